@@ -13,14 +13,21 @@ exactly K / L launches and nothing is computed that is not counted.  `--mode ste
 owns 4096 envs (config 4 = 8 x 4096); the only collective is one RCCL all-reduce of the 8 episode counters.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--mode lookahead|step|graph|rollout] [--workload rvo10|ga3c20|crowd50_laser]
+                    [--full] [--dump-outputs DIR]
 The default workload is the metric's; `ga3c20` (BASELINE config 3: 4096 x 20 GA3C-CADRL agents, network on the fp32
 matrix cores) and `crowd50_laser` (config 5: 4096 x 50 RVO agents + static map + LaserScanSensor) are the "next" rows,
 measured with the same harness and reported with their own roofline (profiles/).
 N>1: either the driver's launcher form  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 or plain  python bench.py --gpus N  (no WORLD_SIZE in the environment): bench.py then starts the N ranks itself with that
 same launcher.  Either way one rank per GPU; the line is refused unless exactly N ranks took part.  Rank 0 prints ONE
-JSON line.  The timed block of EXACTLY K steps is repeated until >= 0.5 s of device time has been measured and the
-MEDIAN block is reported (`timed_blocks` carries first / min / max).
+JSON line.
+A plain run sets up, warms up (W + BURN_IN_STEPS steps, then >= 0.3 s of launches after which the simulator state is put
+back to where it was), times ONE block of EXACTLY K steps and prints the line: the steps it computes depend on its arguments
+alone, so `--dump-outputs DIR` (what the last timed step handed its caller, as .npy files) can be compared between two
+builds.  `--full` adds everything else this script measures: the timed block repeated until >= 0.5 s of device time has
+been measured with the MEDIAN block reported (`timed_blocks` carries first / min / max), the single-launch / rollout /
+two-stream / env-API figures beside the headline, the timed roofline of the ga3c20 / crowd50_laser workloads and the CPU
+baseline.
 """
 import argparse
 import json
@@ -239,12 +246,10 @@ def _time_launches(fn, n, torch, dev):
 
 
 def extra_workload(out, a, sim, core, E, N, K, dev, torch):
-    """metric / config / roofline of the 'next'-row workloads (not the driver's default line)"""
+    """metric / config / roofline of the 'next'-row workloads (not the driver's default line).  The roofline times
+    launches of its own: measured with --full only (a plain line carries `roofline: null` for these workloads)."""
     n = max(20, min(a.steps, 200))
     if a.workload == "ga3c20":
-        infer_s = _time_launches(lambda: sim.ga3c(), n, torch, dev)
-        rows = sim.ga3c_rows()   # agents evaluated by the timed launches (live GA3C-CADRL agents, packed by cagpu_ga3c)
-        flops = 2.0 * GA3C_MACS * rows
         out["metric"] = "agent-steps/sec at 4096 envs x 20 agents (GA3C-CADRL)"
         out["dtype"] = ("f32 network: float32 operands as two fp16 planes (hi + lo = 22 significant bits, fp16 denormals kept), 3 of the 4 "
                         "plane products on the f16 matrix cores (v_mfma_f32_16x16x32_f16, f32 accumulate; a product within 2^-21), layer1's host inputs "
@@ -254,6 +259,12 @@ def extra_workload(out, a, sim, core, E, N, K, dev, torch):
                                      "closest_last, fixture n20 (reference generator, seed 0), auto-reset; one cagpu_ga3c "
                                      "+ one cagpu_step launch per step%s" % (E, N, "; FUSED sensing: the network kernel computes its "
                                      "observation rows from the state (obs = NULL)" if a.ga3c_fused else ""))
+        if not a.full:
+            out["roofline"] = None
+            return
+        infer_s = _time_launches(lambda: sim.ga3c(), n, torch, dev)
+        rows = sim.ga3c_rows()   # agents evaluated by the timed launches (live GA3C-CADRL agents, packed by cagpu_ga3c)
+        flops = 2.0 * GA3C_MACS * rows
         # the roofline of a float32 contraction done this way: every product costs three f16 plane products
         peak = BF16_MFMA_PEAK_TFLOPS / GA3C_PLANE_PRODUCTS
         issued = 2.0 * rows * (GA3C_MACS_BF16 * GA3C_PLANE_PRODUCTS) / infer_s / 1e12
@@ -275,14 +286,17 @@ def extra_workload(out, a, sim, core, E, N, K, dev, torch):
                                    "others), 19 live LSTM steps each (every agent of a 20-agent env observes 19 others); "
                                    "cagpu_ga3c packs those rows first (CaNet.rows_scratch)" % rows}
     else:
-        step_s = _time_launches(lambda: sim.step(), n, torch, dev)
-        scan_s = _time_launches(lambda: sim.laserscan(), n, torch, dev)
-        b = (104 + 28 * K + 3 * 512 * 4) * E * N
         out["metric"] = "agent-steps/sec at 4096 envs x 50 agents (RVO) + LaserScanSensor"
         out["config"]["workload"] = ("configs[4]: %d envs/GPU x %d agents dense crowd, RVOPolicy + static map (160 x 160 "
                                      "cells, wall collisions) + LaserScanSensor 512 beams x 60 samples x 3 scans + "
                                      "OtherAgentsStatesSensor K=%d, fixture n50 (make_testcase_huge, seed 0), auto-reset; "
                                      "one cagpu_step_map + one cagpu_laserscan launch per step" % (E, N, K))
+        if not a.full:
+            out["roofline"] = None
+            return
+        step_s = _time_launches(lambda: sim.step(), n, torch, dev)
+        scan_s = _time_launches(lambda: sim.laserscan(), n, torch, dev)
+        b = (104 + 28 * K + 3 * 512 * 4) * E * N
         out["roofline"] = {"bound": "hbm", "achieved": b / (step_s + scan_s) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                            "frac": b / (step_s + scan_s) / 1e9 / HBM_PEAK_GBS, "traffic": None,
                            "kernel": "ca_kernel + scan_kernel", "avg_launch_us": (step_s + scan_s) * 1e6,
@@ -320,6 +334,55 @@ def crowd_map():
     grid[116:120, 30:130] = True
     grid[60:100, 78:82] = True
     return grid
+
+
+# untimed steps on top of --warmup before the timed block.  Every env starts its first episode at the reset, with every
+# agent active -- about twice the work per step of a long run, where the envs' episodes (~100 - 500 steps on the fixture
+# tables) are at mixed phases and about half the agents are done.  After 1000 steps the active share has settled: the CPU
+# oracle, RVO agents on the fixture tables (512 / 256 / 64 envs of n10 / n20 / n50, auto-reset), gives a mean active share
+# over steps 1000 - 1500 of 0.491 / 0.360 / 0.343 against 0.497 / 0.364 / 0.310 over steps 2000 - 2500 (1.0 at the reset).
+# On the MI355X a single timed block after this burn-in matched the median of the blocks timed after ~0.3 s of steps:
+# rvo10 at 20 and 2000 steps per block and ga3c20 at 100 within 0.6 %.
+BURN_IN_STEPS = 1000
+
+
+def sim_state(sim):
+    """the device tensors that carry a simulator from one step to the next: the state slab (core.BatchedSim's state
+    arrays), the outputs of the step last handed out (the GA3C-CADRL network of the next step reads its observation rows,
+    core.BatchedSim.ga3c), the network's action buffer and, with a static map, the laser scan's history.  (Read after
+    sync(), which rebinds the outputs in look-ahead mode: a restore copies into the tensors current at that moment.)"""
+    sim.sync()
+    return [t for t in (sim._slab, sim._obs, sim._rewards, sim._done, sim._game_over, sim._ga3c_ext,
+                        getattr(sim, "scan_hist", None)) if t is not None]
+
+
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs: array bytes at most (the .npy headers on top stay far below 64 MB in all)
+DUMP_SEED = 0
+
+
+def dump_outputs(sim, workload, path):
+    """--dump-outputs: what the last timed step handed its caller -- obs, rewards, done, game_over of every env (and the
+    laser scan of crowd50_laser) -- as float32 <path>/<name>.npy (done / game_over as 0 / 1).  Beyond DUMP_BYTES the
+    same fixed, seeded sample of envs (sorted env indices) is taken from every array.  -> the record for the JSON line"""
+    import torch
+    outs = {"obs": sim.obs, "rewards": sim.rewards, "done": sim.done, "game_over": sim.game_over}
+    if workload == "crowd50_laser":
+        outs["laserscan"] = sim.scan
+    E = sim.E
+    per_env = sum(t.numel() // E for t in outs.values()) * 4
+    idx = None
+    if per_env * E > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(E, max(1, DUMP_BYTES // per_env), replace=False))
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, t in outs.items():
+        if idx is not None:
+            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        arr = t.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        shapes[name] = list(arr.shape)
+    return {"dir": path, "dtype": "float32", "arrays": shapes, "envs": E if idx is None else len(idx), "of_envs": E,
+            "sample": None if idx is None else "numpy default_rng(%d).choice(%d, %d, replace=False), sorted" % (DUMP_SEED, E, len(idx))}
 
 
 def valu_block(E, N, kernel, step_s):
@@ -391,24 +454,38 @@ def main():
                     help="N = 1: initialise torch.distributed (--backend, default nccl = RCCL) with world_size 1 anyway and "
                          "run every collective of the N > 1 path (barriers, the MAX all-reduce of the block table, the "
                          "episode-statistics all-reduce, the all-gather of per-rank times)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline line: the repeated timed blocks (--min-timed-seconds 0.5 unless "
+                         "given), the single-launch / rollout / two-stream / env-API figures, the timed roofline of the "
+                         "ga3c20 / crowd50_laser workloads and the CPU baseline.  Without it: ONE timed block of exactly "
+                         "--steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them handed its caller (obs, rewards, done, game_over; "
+                         "+ laserscan for crowd50_laser) as float32 DIR/<name>.npy, at most 60 MB (a fixed seeded sample of "
+                         "envs beyond that).  The steps computed before it depend on the arguments alone unless repeated timed "
+                         "blocks are asked for (--full, --min-timed-seconds)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--ga3c-fused", action="store_true",
                     help="ga3c20: cagpu_ga3c computes the observation rows it needs from the state itself (obs = NULL: sensing + "
                          "inference fused in one kernel) instead of reading the rows the step kernel stored")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="A/B: without CaState.next_action, i.e. the unpipelined step kernel (policy query at the start of the step)")
     ap.add_argument("--min-warm-seconds", type=float, default=0.3,
-                    help="untimed steady-state warm-up on top of --warmup (launches until this much time has passed)")
-    ap.add_argument("--min-timed-seconds", type=float, default=0.5,
+                    help="untimed steady-state warm-up on top of --warmup and the burn-in (launches until this much time has "
+                         "passed; the simulator state is then put back to where it was before them)")
+    ap.add_argument("--min-timed-seconds", type=float, default=None,
                     help="the timed block of EXACTLY --steps steps is repeated until this much device time has been measured "
-                         "(at most --max-blocks blocks); the line reports the MEDIAN block.  0: a single block")
+                         "(at most --max-blocks blocks); the line reports the MEDIAN block.  0: a single block; default 0.5 "
+                         "with --full, else 0")
     ap.add_argument("--max-blocks", type=int, default=1000)
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the rollout / two-stream extras (profiling runs: only the headline kernel is launched)")
+                    help="with --full: skip the rollout / two-stream extras (profiling runs: only the headline kernel is launched)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL over xGMI)")
     ap.add_argument("--share-device", action="store_true",
                     help="testing only: every rank uses cuda:0 (lets a 1-GPU box exercise the N>1 code path with gloo)")
     a = ap.parse_args()
+    if a.min_timed_seconds is None:
+        a.min_timed_seconds = 0.5 if a.full else 0.0
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn(a)   # does not return
@@ -484,17 +561,21 @@ def main():
 
     # ---- untimed: one pass through the statistics reduction (its first call loads the reduce kernel's code object
     # and, for N > 1, builds the RCCL communicator) and through the timing events (torch creates them lazily), the
-    # caller's W warm-up steps, then launches until the device has been busy for >= 0.3 s (clocks and caches in steady
-    # state whatever W was).  The warm-up ends directly at the synchronize that opens the timed region: no idle gap in
-    # which the device could drop its clocks.
+    # caller's W warm-up steps and BURN_IN_STEPS more, then launches until the device has been busy for >= 0.3 s (clocks
+    # and caches in steady state whatever W was).  How many steps that is depends on the clock, so the simulator is then
+    # put back to the state it had after the W + BURN_IN_STEPS steps: the steps timed below (and what --dump-outputs
+    # writes) are a function of the arguments alone.  The warm-up ends directly at the synchronize that opens the timed
+    # region: no idle gap in which the device could drop its clocks.
     import gc
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev0.record()
     ev1.record()
     reduce_episode_stats(sim.episode_stats(), world, force=dist_on)
     chunk = 50 if a.mode in ("step", "graph") else (a.steps if a.mode == "rollout" else L * max(1, 50 // L))
-    run(a.warmup if a.mode != "lookahead" else -(-a.warmup // L) * L)   # (whole rings: a timed block starts at a ring boundary)
+    warmup = a.warmup + BURN_IN_STEPS
+    run(warmup if a.mode != "lookahead" else -(-warmup // L) * L)   # (whole rings: a timed block starts at a ring boundary)
     torch.cuda.synchronize(dev)
+    state0 = [t.clone() for t in sim_state(sim)] if a.min_warm_seconds > 0 else None
     if a.mode == "graph":  # capture the launches of K steps (and of the warm-up chunk) once; run() then replays them
         for n in sorted({a.steps, 50}):
             g = torch.cuda.CUDAGraph()
@@ -508,6 +589,13 @@ def main():
     t_w = time.perf_counter()
     while time.perf_counter() - t_w < a.min_warm_seconds:
         run(chunk)
+        torch.cuda.synchronize(dev)
+    if state0 is not None:
+        now = sim_state(sim)
+        assert [t.shape for t in now] == [t.shape for t in state0]
+        for t, t0_ in zip(now, state0):
+            t.copy_(t0_)
+        del state0
         torch.cuda.synchronize(dev)
 
     # ---- timed: a BLOCK is EXACTLY a.steps steps between barrier + synchronize on both sides, nothing else inside.  One
@@ -552,6 +640,8 @@ def main():
     stats_local = sim.episode_stats()
     stats = reduce_episode_stats(stats_local, world, force=dist_on)   # the only collective (8 counters), outside the clock
     torch.cuda.synchronize(dev)
+    # (before anything below launches another step: the extras of --full run on the same simulator)
+    dumped = dump_outputs(sim, a.workload, a.dump_outputs) if a.dump_outputs and rank == 0 else None
     # ---- multi-GPU evidence the driver can read from the JSON line: ranks seen, per-rank device time of the SAME K
     # steps, and the latency of the one collective (the 8-counter all-reduce), measured outside the step clock
     per_rank_ms, allreduce_us = [gpu_ms_local / a.steps], None
@@ -642,9 +732,11 @@ def main():
             "episode_stats_per_rank": per_rank_stats,   # (N > 1 / --force-dist: the all-gathered shard counters; their sum is episode_stats)
             "provenance": provenance(),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if a.workload != "rvo10":
             extra_workload(out, a, sim, core, E, N, K, dev, torch)
-        extras = world == 1 and a.mode in ("step", "lookahead") and a.workload == "rvo10" and not a.no_extras
+        extras = a.full and world == 1 and a.mode in ("step", "lookahead") and a.workload == "rvo10" and not a.no_extras
         if extras and a.mode == "lookahead":
             # beside the headline: the same workload one cagpu_step launch per step (what a caller with external actions gets)
             n1 = max(a.steps, 500)
@@ -718,7 +810,7 @@ def main():
                                           "overlap, so the roofline above is quoted for the single-chain launch" % (E // 2, nrep)}
         if extras:
             out["env_api"] = env_api_rates(E, N, min(max(a.steps, 640), 1280), torch, dev)
-        if world == 1 and not a.no_cpu_baseline and a.workload == "rvo10":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload == "rvo10":
             out["cpu_baseline"] = cpu_baseline(N, K)
         print(json.dumps(out))
     if dist_on:

@@ -9,11 +9,11 @@ echo "tests rc=$?" >> $O/tests.log
 tail -n 3 $O/tests.log
 PREV=$PWD/gym_collision_avoidance_amd/libcagpu_prev.so
 for rep in 1 2; do
-  timeout 300 python bench.py --workload ga3c20 --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_new_$rep.json 2> $O/cfg3_new_$rep.err
-  CAGPU_LIB=$PREV timeout 300 python bench.py --workload ga3c20 --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_prev_$rep.json 2> $O/cfg3_prev_$rep.err
+  timeout 300 python bench.py --full --workload ga3c20 --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_new_$rep.json 2> $O/cfg3_new_$rep.err
+  CAGPU_LIB=$PREV timeout 300 python bench.py --full --workload ga3c20 --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_prev_$rep.json 2> $O/cfg3_prev_$rep.err
 done
-timeout 300 python bench.py --workload ga3c20 --ga3c-fused --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_fused_new_1.json 2> $O/cfg3_fused_new_1.err
-CAGPU_LIB=$PREV timeout 300 python bench.py --workload ga3c20 --ga3c-fused --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_fused_prev_1.json 2> $O/cfg3_fused_prev_1.err
+timeout 300 python bench.py --full --workload ga3c20 --ga3c-fused --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_fused_new_1.json 2> $O/cfg3_fused_new_1.err
+CAGPU_LIB=$PREV timeout 300 python bench.py --full --workload ga3c20 --ga3c-fused --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_fused_prev_1.json 2> $O/cfg3_fused_prev_1.err
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/cfg3_ab/cfg3_*.json")):

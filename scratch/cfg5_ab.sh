@@ -10,11 +10,11 @@ echo "tests rc=$?" >> $O/tests.log
 tail -n 3 $O/tests.log
 PREV=$PWD/gym_collision_avoidance_amd/libcagpu_prev.so
 for rep in 1 2; do
-  timeout 300 python bench.py --workload crowd50_laser --steps 50 --warmup 5 --no-cpu-baseline > $O/cfg5_new_$rep.json 2> $O/cfg5_new_$rep.err
-  CAGPU_LIB=$PREV timeout 300 python bench.py --workload crowd50_laser --steps 50 --warmup 5 --no-cpu-baseline > $O/cfg5_prev_$rep.json 2> $O/cfg5_prev_$rep.err
+  timeout 300 python bench.py --full --workload crowd50_laser --steps 50 --warmup 5 --no-cpu-baseline > $O/cfg5_new_$rep.json 2> $O/cfg5_new_$rep.err
+  CAGPU_LIB=$PREV timeout 300 python bench.py --full --workload crowd50_laser --steps 50 --warmup 5 --no-cpu-baseline > $O/cfg5_prev_$rep.json 2> $O/cfg5_prev_$rep.err
 done
-timeout 300 python bench.py --workload ga3c20 --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_new_1.json 2> $O/cfg3_new_1.err
-CAGPU_LIB=$PREV timeout 300 python bench.py --workload ga3c20 --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_prev_1.json 2> $O/cfg3_prev_1.err
+timeout 300 python bench.py --full --workload ga3c20 --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_new_1.json 2> $O/cfg3_new_1.err
+CAGPU_LIB=$PREV timeout 300 python bench.py --full --workload ga3c20 --steps 100 --warmup 10 --no-cpu-baseline > $O/cfg3_prev_1.json 2> $O/cfg3_prev_1.err
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/cfg5_ab/cfg*.json")):

@@ -13,10 +13,10 @@ for lib in "$@"; do
   echo "$n tests rc=$? $(tail -n 1 $O/tests_$n.log)"
 done
 for rep in 1 2; do
-  timeout 300 python bench.py --workload crowd50_laser --steps 50 --warmup 5 --no-cpu-baseline > $O/cfg5_product_$rep.json 2> $O/cfg5_product_$rep.err
+  timeout 300 python bench.py --full --workload crowd50_laser --steps 50 --warmup 5 --no-cpu-baseline > $O/cfg5_product_$rep.json 2> $O/cfg5_product_$rep.err
   for lib in "$@"; do
     n=$(basename $lib .so)
-    CAGPU_LIB=$PWD/$lib timeout 300 python bench.py --workload crowd50_laser --steps 50 --warmup 5 --no-cpu-baseline > $O/cfg5_${n}_$rep.json 2> $O/cfg5_${n}_$rep.err
+    CAGPU_LIB=$PWD/$lib timeout 300 python bench.py --full --workload crowd50_laser --steps 50 --warmup 5 --no-cpu-baseline > $O/cfg5_${n}_$rep.json 2> $O/cfg5_${n}_$rep.err
   done
 done
 python - <<'PY'

@@ -7,7 +7,7 @@ rm -rf $O; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 for lib in "$@"; do
   n=$(basename "$lib" .so)
-  P="python $R/bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 500 --min-warm-seconds 0"
+  P="python $R/bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 500 --min-warm-seconds 0"
   CAGPU_LIB=$R/$lib timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d "$O/$n" -- $P > "$O/$n.log" 2>&1
 done
 find $O -name '*agent_info.csv' -delete

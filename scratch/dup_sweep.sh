@@ -5,7 +5,7 @@ O=$R/gpurun_out/${TAG:-dup}
 mkdir -p $O
 AB=$R/gym_collision_avoidance_amd/libcagpu_ablate_fast.so
 for ab in 0 256 512 2048 4096 2 32 64 1; do
-  CAGPU_LIB=$AB CAGPU_ABLATE=$ab timeout 200 python bench.py --steps 1000 --warmup 100 --no-cpu-baseline > $O/ab_$ab.json 2> $O/ab_$ab.err
+  CAGPU_LIB=$AB CAGPU_ABLATE=$ab timeout 200 python bench.py --full --steps 1000 --warmup 100 --no-cpu-baseline > $O/ab_$ab.json 2> $O/ab_$ab.err
 done
 python - <<PY
 import json

@@ -7,7 +7,7 @@ mkdir -p $O
 for v in $LIBS; do
   L=$R/gym_collision_avoidance_amd/libcagpu_$v.so
   [ "$v" = product ] && L=$R/gym_collision_avoidance_amd/libcagpu.so
-  CAGPU_LIB=$L timeout 200 python bench.py --steps ${STEPS:-1000} --warmup 100 --no-cpu-baseline ${BARGS} > $O/$v.json 2> $O/$v.err
+  CAGPU_LIB=$L timeout 200 python bench.py --full --steps ${STEPS:-1000} --warmup 100 --no-cpu-baseline ${BARGS} > $O/$v.json 2> $O/$v.err
 done
 LIBS="$LIBS" python - <<PY
 import json, os

@@ -7,7 +7,7 @@ mkdir -p $O
 for rep in 1 2; do
 for lib in "$@"; do
   n=$(basename $lib .so)
-  CAGPU_LIB=$lib timeout 200 python bench.py --no-cpu-baseline --steps 3000 > $O/${n}_$rep.json 2>/dev/null
+  CAGPU_LIB=$lib timeout 200 python bench.py --full --no-cpu-baseline --steps 3000 > $O/${n}_$rep.json 2>/dev/null
 done
 done
 python - <<'PY'

@@ -3,7 +3,7 @@
 R=$PWD; O=$R/gpurun_out/tile; mkdir -p $O
 KN=$R/gym_collision_avoidance_amd/libcagpu_knobs.so
 for t in ${TILES:-0 6}; do for e in ${ENVS:-4096 8192 32768}; do
-  CAGPU_LIB=$KN CAGPU_TILE=$t timeout 200 python bench.py --envs $e --steps 500 --warmup 50 --no-cpu-baseline > $O/t${t}_e$e.json 2> $O/t${t}_e$e.err
+  CAGPU_LIB=$KN CAGPU_TILE=$t timeout 200 python bench.py --full --envs $e --steps 500 --warmup 50 --no-cpu-baseline > $O/t${t}_e$e.json 2> $O/t${t}_e$e.err
   python - <<PY
 import json
 try:

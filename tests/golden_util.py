@@ -115,3 +115,22 @@ def run_suite(sim, cases, flags_of, step, max_steps=4000):
             break
     assert not live.any(), "%d episodes did not end" % live.sum()
     return out
+
+
+# ---------------------------------------------------------------- digests of reference files (oracle/gen_reference_digests.py)
+def digest(arrays):
+    """sha256 over a sequence of arrays, each as float64 (exact for the float32 / float64 data compared here), shape and
+    values in order"""
+    import hashlib
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        h.update(repr(a.shape).encode() + a.tobytes())
+    return h.hexdigest()
+
+
+def reference_digests():
+    """tests/golden/reference_digests.json: digest() of reference files the shipped data must equal"""
+    import json
+    with open(os.path.join(GOLD, "reference_digests.json")) as f:
+        return json.load(f)

@@ -455,7 +455,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29611", WORLD_SIZE="2")
     env.pop("GYM_CONFIG_CLASS", None); env.pop("GYM_CONFIG_PATH", None)
     cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "300", "--warmup", "20", "--envs",
-           "256", "--backend", "gloo", "--share-device", "--no-cpu-baseline"]
+           "256", "--backend", "gloo", "--share-device", "--no-cpu-baseline", "--full"]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
                               stderr=subprocess.PIPE) for r in range(2)]
     outs = [p.communicate(timeout=600) for p in procs]

@@ -486,13 +486,11 @@ def test_carrl_fixture_family_and_huge_testcase():
     seeds = [tc.preset_testCases(2, full_test_suite=True, carrl=True, seed=k) for k in range(5)]
     assert len(plain) == len(carrl) == 500 and all(len(s_) == 500 and s_[0].shape == (2, 6) for s_ in seeds)
     assert not np.array_equal(np.array(plain), np.array(carrl)) and not np.array_equal(np.array(seeds[0]), np.array(seeds[1]))
-    if os.path.isdir("/root/reference"):   # (build container: the data equal the pickles byte for byte)
-        import pickle
-        d = "/root/reference/gym_collision_avoidance/envs/test_cases/"
-        for name, got in (("2_agents_500_cases_carrl.p", carrl), ("2_agents_500_cases_carrl_seed003.p", seeds[3])):
-            with open(d + name, "rb") as f:
-                want = pickle.load(f, encoding="latin1")
-            assert all(np.array_equal(np.asarray(w_, np.float64), g_) for w_, g_ in zip(want, got))
+    # the data equal the reference's pickles value for value (digests recorded by oracle/gen_reference_digests.py)
+    want = gu.reference_digests()["carrl"]
+    assert gu.digest(carrl) == want["2_agents_500_cases_carrl.p"]
+    for k in range(5):
+        assert gu.digest(seeds[k]) == want["2_agents_500_cases_carrl_seed%03d.p" % k], k
     with pytest.raises(FileNotFoundError):
         tc.preset_testCases(3, full_test_suite=True, carrl=True)
     with pytest.raises(FileNotFoundError):

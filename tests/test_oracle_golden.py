@@ -158,12 +158,12 @@ def test_ga3c_network_known_answers_and_checkpoint_reader():
     assert np.array_equal(network.Actions().actions, ACTIONS)
     w = network.load_weights(os.path.join(network.DATA_DIR, "IROS18", "network_01900000"))
     assert w["lstm_kernel"].shape == (71, 256) and w["logits_p_kernel"].shape == (256, 11)
-    ref = "/root/reference/gym_collision_avoidance/envs/policies/GA3C_CADRL/checkpoints/IROS18/network_01900000"
-    if os.path.exists(ref + ".index"):     # in the build container: the raw TF checkpoint parses to the same arrays
-        raw = network.read_checkpoint(ref)
-        assert set(raw) == set(w)
-        for k in raw:
-            assert np.array_equal(raw[k], w[k]), k
+    # the reference's raw TF checkpoint, as the reader parses it, holds the same arrays (digests recorded by
+    # oracle/gen_reference_digests.py)
+    raw = gu.reference_digests()["ga3c_iros18_checkpoint"]
+    assert set(raw) == set(w)
+    for k in raw:
+        assert gu.digest([w[k]]) == raw[k], k
 
 
 def test_ga3c_agents_reach_their_goals_in_the_oracle():
