@@ -14,7 +14,7 @@ AT_GOAL, WAS_AT_GOAL, IN_COLLISION, WAS_IN_COLLISION, OUT_OF_TIME, DONE, IS_LEAR
     1 << 0, 1 << 1, 1 << 2, 1 << 3, 1 << 4, 1 << 5, 1 << 6, 1 << 7)
 POLICY_SHIFT, DYNAMICS_SHIFT = 8, 12
 ABSENT, PLAN_VALID = 1 << 16, 1 << 17
-ABI_VERSION = 11  # CAGPU_VERSION of include/cagpu.h: the struct layouts below mirror THAT header
+ABI_VERSION = 12  # CAGPU_VERSION of include/cagpu.h: the struct layouts below mirror THAT header
 POL_RVO, POL_NONCOOP, POL_STATIC, POL_EXTERNAL, POL_LEARNING, POL_LEARNING_GA3C, POL_GA3C_CADRL = range(7)
 DYN_UNICYCLE, DYN_MAX_TURN_RATE, DYN_EXTERNAL = range(3)
 SORT_CLOSEST_FIRST, SORT_CLOSEST_LAST, SORT_TIME_TO_IMPACT = range(3)
@@ -57,6 +57,11 @@ class CaMap(C.Structure):
                 ("origin_r", C.c_double), ("origin_c", C.c_double)]
 
 
+class CaMapSet(C.Structure):
+    _fields_ = [("map", CaMap), ("env_map", _P), ("num_maps", C.c_int32), ("reserved0", C.c_int32),
+                ("map_seed", C.c_uint64)]
+
+
 class CaScan(C.Structure):
     _fields_ = [("hist", _P), ("out", _P), ("num_beams", C.c_int32), ("num_to_store", C.c_int32),
                 ("num_ranges", C.c_int32), ("reserved0", C.c_int32), ("min_angle", C.c_double),
@@ -74,7 +79,8 @@ class CaNet(C.Structure):
 
 EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_reset", "cagpu_step", "cagpu_step_map", "cagpu_rollout",
            "cagpu_orca", "cagpu_observe", "cagpu_laserscan", "cagpu_ga3c", "cagpu_generate_cases", "cagpu_generate_cases_ragged", "cagpu_plan", "cagpu_debug_libm", "cagpu_device_faults", "cagpu_workspace_bytes",
-           "cagpu_ga3c_packed_bytes", "cagpu_ga3c_pack", "cagpu_rollout_ring", "cagpu_ring_snapshots", "cagpu_debug_copy8", "cagpu_device_faults_async")
+           "cagpu_ga3c_packed_bytes", "cagpu_ga3c_pack", "cagpu_rollout_ring", "cagpu_ring_snapshots", "cagpu_debug_copy8", "cagpu_device_faults_async",
+           "cagpu_step_maps", "cagpu_laserscan_maps")
 
 _lib = None
 
@@ -107,6 +113,8 @@ def lib():
     L.cagpu_debug_copy8.argtypes = [C.c_int64, _P, _P, _P]
     L.cagpu_step_map.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaMap), _P]
     L.cagpu_laserscan.argtypes = [PP, PS, C.POINTER(CaMap), C.POINTER(CaScan), _P]
+    L.cagpu_step_maps.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaMapSet), _P]
+    L.cagpu_laserscan_maps.argtypes = [PP, PS, C.POINTER(CaMapSet), C.POINTER(CaScan), _P]
     L.cagpu_observe.argtypes = [PP, PS, PO, _P]
     L.cagpu_plan.argtypes = [PP, PS, _P]
     L.cagpu_orca.argtypes = [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int32,

@@ -125,6 +125,9 @@ class BatchedSim(object):
         self._table = None
         self._keep = []
         self._map = None
+        self._maps = None         # a map set (set_map with a stack of maps): CaMapSet; env_map is its device index tensor
+        self._map_rng = None      # the generator of the map-set key an explicit reset() draws (set_map's map_seed)
+        self.env_map = None
         self._scan = None
         self.scan = None
         self.ga3c_fused = False   # cagpu_ga3c with obs = NULL: sensing fused into the network kernel (see ga3c())
@@ -462,6 +465,9 @@ class BatchedSim(object):
                                        None if h is None else h.data_ptr(), None if m is None else m.data_ptr(),
                                        self._stream()))
         self._keep = [c, h, m]  # keep alive until the stream has consumed them
+        if self._maps is not None and self._map_rng is not None:
+            # a fresh key per explicit reset: the auto-reset draws of the new episodes are not those of the last ones
+            self._maps.map_seed = int(self._map_rng.integers(1, 1 << 64, dtype=np.uint64))
         self._apply_sensor_variants()
         return self._obs
 
@@ -473,24 +479,43 @@ class BatchedSim(object):
         return self.reset(self._table[idx])
 
     def set_map(self, static_map=None, rows=160, cols=160, cell=0.1, num_beams=512, num_to_store=3, max_range=6.0,
-                range_res=0.1, min_angle=-math.pi / 2, max_angle=math.pi / 2):
+                range_res=0.1, min_angle=-math.pi / 2, max_angle=math.pi / 2, env_map=None, map_seed=0):
         """Static occupancy grid (Map.py:6-24; bool [rows, cols], True = occupied, or None for an empty map) + the
         LaserScanSensor buffers with the reference's hard-coded parameters (LaserScanSensor.py:28-39).  With a map
-        set, step() also tests wall collisions (collision_avoidance_env.py:494-506)."""
+        set, step() also tests wall collisions (collision_avoidance_env.py:494-506).
+
+        A MAP SET (include/cagpu.h CaMapSet): `static_map` a bool stack [M, rows, cols] -- every env has its own map,
+        the device int32 tensor `env_map` [E] (default: env e on map e % M; an explicit one must hold indices in
+        [0, M)), and step() / laserscan() run the cagpu_step_maps / cagpu_laserscan_maps entry points.  map_seed != 0:
+        every auto-reset of an env draws its next map on the device (the reference draws a map per episode,
+        collision_avoidance_env.py:274-275, :384-385) with a key that every explicit reset() draws anew from a generator
+        seeded by map_seed (`map_seed` property: the key in force); 0: every env keeps its map."""
         self.sync()
         bits = None
         self._fast_args = None
+        self._maps, self._map_rng, self.env_map = None, None, None
+        M = 0
         if static_map is not None:
             m = np.asarray(static_map).astype(bool)
-            assert m.shape == (rows, cols), m.shape
+            M = m.shape[0] if m.ndim == 3 else 0
+            if m.shape != ((M, rows, cols) if M else (rows, cols)) or (m.ndim == 3 and M < 1):
+                raise ValueError("static map of shape %s: expected [%d, %d] or a stack [M, %d, %d]" % (m.shape, rows, cols,
+                                                                                                        rows, cols))
             wpr = (cols + 31) // 32
-            pad = np.zeros((rows, wpr * 32), dtype=np.uint8)
-            pad[:, :cols] = m
-            words = np.packbits(pad.reshape(rows, wpr, 32), axis=-1, bitorder="little").view(np.uint32).reshape(rows, wpr)
-            bits = torch.from_numpy(words.view(np.int32).copy()).to(self.device)
+            pad = np.zeros(m.shape[:-1] + (wpr * 32,), dtype=np.uint8)
+            pad[..., :cols] = m
+            words = np.packbits(pad.reshape(m.shape[:-1] + (wpr, 32)), axis=-1, bitorder="little").view(np.uint32)
+            bits = torch.from_numpy(words.reshape(-1).view(np.int32).copy()).to(self.device)
         self._map_bits = bits
         self._map = nat.CaMap(static_bits=None if bits is None else bits.data_ptr(), rows=rows, cols=cols, cell=cell,
                               origin_r=(rows * cell / 2.) / cell, origin_c=(cols * cell / 2.) / cell)
+        if M:
+            self.env_map = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
+            self._maps = nat.CaMapSet(map=self._map, env_map=self.env_map.data_ptr(), num_maps=M, map_seed=0)
+            self.set_env_map(np.arange(self.E) % M if env_map is None else env_map)
+            if int(map_seed):
+                self._map_rng = np.random.Generator(np.random.PCG64(int(map_seed) & 0xFFFFFFFFFFFFFFFF))
+                self._maps.map_seed = int(map_seed) & 0xFFFFFFFFFFFFFFFF
         R = len(np.arange(0, max_range, range_res))
         self.scan_hist = torch.full((self.E, self.N, num_to_store, num_beams), 255, dtype=torch.uint8,
                                     device=self.device)
@@ -499,12 +524,45 @@ class BatchedSim(object):
                                 num_to_store=num_to_store, num_ranges=R, min_angle=min_angle, max_angle=max_angle,
                                 range_res=range_res, max_range=max_range)
 
+    @property
+    def num_maps(self):
+        """maps of the attached map set (0: none -- one map, or none, for every env)"""
+        return 0 if self._maps is None else int(self._maps.num_maps)
+
+    @property
+    def map_seed(self):
+        """the key of the map set's auto-reset draws in force (CaMapSet.map_seed; 0: an auto-reset keeps the env's map)"""
+        return 0 if self._maps is None else int(self._maps.map_seed)
+
+    def set_map_seed(self, key):
+        """replace the key of the map set's auto-reset draws (0: off); the next explicit reset() draws a new one only
+        where set_map was given a map_seed"""
+        assert self._maps is not None, "set_map() with a stack of maps first"
+        self._maps.map_seed = int(key) & 0xFFFFFFFFFFFFFFFF
+
+    def set_env_map(self, env_map):
+        """the map of every env of the map set: ints broadcastable to [E], each in [0, M) (checked here: the device
+        only flags an index outside, bit 2 of the fault word, and gives that env an empty map)"""
+        assert self._maps is not None, "set_map() with a stack of maps first"
+        self.sync()
+        idx = np.array(np.broadcast_to(np.asarray(env_map), (self.E,)))
+        if not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError("env_map must hold integers, got %s" % idx.dtype)
+        M = int(self._maps.num_maps)
+        if idx.size and (idx.min() < 0 or idx.max() >= M):
+            raise ValueError("env_map holds indices outside [0, %d): %s" % (M, sorted(set(idx[(idx < 0) | (idx >= M)].tolist()))[:8]))
+        self.env_map.copy_(torch.from_numpy(idx.astype(np.int32)))   # (in place: the CaMapSet points at this tensor)
+
     def laserscan(self):
         """'laserscan' observation [E,N,num_to_store,num_beams] of the current state (call after reset / step)."""
         assert self._map is not None, "set_map() first"
         self.sync()
-        nat.check(self.lib.cagpu_laserscan(C.byref(self.p), C.byref(self._cs), C.byref(self._map),
-                                           C.byref(self._scan), self._stream()))
+        if self._maps is not None:
+            nat.check(self.lib.cagpu_laserscan_maps(C.byref(self.p), C.byref(self._cs), C.byref(self._maps),
+                                                    C.byref(self._scan), self._stream()))
+        else:
+            nat.check(self.lib.cagpu_laserscan(C.byref(self.p), C.byref(self._cs), C.byref(self._map),
+                                               C.byref(self._scan), self._stream()))
         return self.scan
 
     def _new_outputs(self, keep=False):
@@ -535,7 +593,10 @@ class BatchedSim(object):
             fa = self._fast_args
             if fa is None:
                 ar = None if self._ar is None else C.byref(self._ar)
-                if self._map is not None:
+                if self._maps is not None:
+                    fa = (self.lib.cagpu_step_maps, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
+                                                     C.byref(self._maps)))
+                elif self._map is not None:
                     fa = (self.lib.cagpu_step_map, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
                                                     C.byref(self._map)))
                 else:
@@ -564,7 +625,12 @@ class BatchedSim(object):
             e = self.ga3c(None if e is None else self._ga3c_ext)
         if self.fresh_outputs:
             self._new_outputs()
-        if self._map is not None:
+        if self._maps is not None:
+            nat.check(self.lib.cagpu_step_maps(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
+                                               None if e is None else e.data_ptr(),
+                                               None if self._ar is None else C.byref(self._ar), C.byref(self._maps),
+                                               self._stream()))
+        elif self._map is not None:
             nat.check(self.lib.cagpu_step_map(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
                                               None if e is None else e.data_ptr(),
                                               None if self._ar is None else C.byref(self._ar), C.byref(self._map),
@@ -795,9 +861,10 @@ class BatchedSim(object):
         with torch.cuda.device(self.device):
             f = nat.device_faults(clear=True)
         if f:
-            raise nat.CagpuError("device fault word 0x%x:%s%s the simulator state is not to be trusted" % (
+            raise nat.CagpuError("device fault word 0x%x:%s%s%s the simulator state is not to be trusted" % (
                 f, " a hand-over inside the pipelined step kernel timed out;" if f & 1 else "",
-                " a GA3C-CADRL operand left the fp16 range of the network kernel's two-plane split (|x| >= 65504);" if f & 2 else ""))
+                " a GA3C-CADRL operand left the fp16 range of the network kernel's two-plane split (|x| >= 65504);" if f & 2 else "",
+                " bit 2: a map-set env's map index (env_map) lay outside [0, num_maps), that env saw an empty map;" if f & 4 else ""))
 
     def episode_stats(self, check=True):
         """Per-shard episode counters: float64 [8] (see STAT_NAMES), reduced on the device.  A reporting point: the

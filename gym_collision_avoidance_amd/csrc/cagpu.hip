@@ -78,7 +78,23 @@ struct KArgs {
   int32_t launch_seq;  // a per-process launch counter: tags the words of the n-step kernel's per-CU progress table (cagpu_pipe.inc)
   float inv_h_f, inv_dt_f;  // pipelined kernels: 1.0f / float(p.rvo_time_horizon), 1.0f / float(p.rvo_dt) -- IEEE float quotients, set by launch_pipe2
   int32_t yield_t;     // > 0: progress-fair priorities among the workgroups of a CU (PIPE_PRIO in cagpu_pipe.inc); set by launch_pipe2
+  // map set (cagpu_step_maps; env_map == nullptr everywhere else): env e's grid is map.static_bits + env_map[e] * map_words.
+  // Only the single-step kernels read these (the n-step instantiations compile the set code out).
+  int32_t* env_map;
+  int64_t map_words;         // rows * words per row: one map of the set
+  int32_t num_maps;
+  unsigned long long map_seed;  // != 0: an auto-reset draws the env's next map (CaMapSet.map_seed)
 };
+
+// A map-set env's grid (KArgs / ScanArgs .env_map): map m of the set, or nullptr -- no walls, no map memory read -- for an
+// index outside [0, num_maps), which raises bit 2 of the fault word when `report` (one lane per env reports).
+__device__ unsigned int g_fault = 0u;
+__device__ __forceinline__ const uint32_t* set_grid(const uint32_t* bits, const long words, const int num_maps, const int m,
+                                                    const bool report) {
+  if (m >= 0 && m < num_maps) return bits + static_cast<long>(m) * words;
+  if (report) atomicOr(&g_fault, 4u);
+  return nullptr;
+}
 
 // ---------------------------------------------------------------- small math helpers
 struct F2 {
@@ -468,9 +484,9 @@ __device__ double time_to_impact(double hx, double hy, double ox, double oy, dou
   return d / sqrt(v0 * v0 + v1 * v1);
 }
 
-// The device's fault word (cagpu_device_faults): bit 0 = a bounded hand-over poll of the pipelined step kernel ran out
-// (cagpu_pipe.inc), bit 1 = a GA3C-CADRL operand left the fp16 range of the network kernel's two-plane split (cagpu_ga3c.inc).
-__device__ unsigned int g_fault = 0u;
+// The device's fault word (cagpu_device_faults; defined above KArgs' set_grid): bit 0 = a bounded hand-over poll of the
+// pipelined step kernel ran out (cagpu_pipe.inc), bit 1 = a GA3C-CADRL operand left the fp16 range of the network kernel's
+// two-plane split (cagpu_ga3c.inc), bit 2 = a map-set env's map index lay outside [0, num_maps) (set_grid).
 
 #include "cagpu_grouplp.inc"
 
@@ -574,6 +590,16 @@ __host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~static_
 #include "cagpu_scan.inc"
 #include "cagpu_ga3c.inc"
 #include "cagpu_gen.inc"
+
+// The map a map-set env takes at its k-th auto-reset (CaMapSet.map_seed): min(floor(M u), M - 1), u the Philox uniform of
+// (seed; global env id lo, hi, k, 0xFFFFFFFF) -- the reset headings' construction with a last counter word no agent index has
+__device__ __forceinline__ int32_t map_draw(const unsigned long long seed, const long ge, const int k, const int num_maps) {
+  const unsigned long long g = static_cast<unsigned long long>(ge);
+  const double u = gen::uniform_at(seed, static_cast<unsigned>(g), static_cast<unsigned>(g >> 32), static_cast<unsigned>(k),
+                                   0xFFFFFFFFu);
+  const int m = static_cast<int>(floor(num_maps * u));
+  return m < num_maps - 1 ? m : num_maps - 1;
+}
 
 // fixed: 7 f64 + 10 f32 + 4 u32 per agent slot (the 3 f64 of the episode scratch alias six ORCA float arrays) + the
 // linearProgram3 queue (length + up to ROW entries, then the number of ORCA queries)
@@ -1388,6 +1414,15 @@ LP1_UNROLL
       // ---- A3 (wave 0, while the other waves finish the pair items of P4): rewards + collision flag (env.py:394-456),
       // observation scalars
       if (wave0) PRIO(3, 0, 3, 3, 3, 3, 3, 3);
+      // a map set (single-step kernel only; workgroup-uniform test): the env's grid, its index read by the env's agent 0
+      // lane and handed to the others -- the wall tests of this step see the map the env had when the step began
+      const uint32_t* wall_bits = nullptr;
+      const bool wall_set = !MULTI && k.env_map != nullptr && k.mode == MODE_STEP && pass == 0;
+      if (wall_set && wave0) {
+        int m = (active && a == 0) ? k.env_map[e] : 0;
+        m = __shfl(m, ebase);
+        wall_bits = active ? set_grid(k.map.static_bits, k.map_words, k.num_maps, m, a == 0) : nullptr;
+      }
       if (wave0 && active) {
         if (k.mode == MODE_STEP && pass == 0) {
           double nearest = INFINITY;
@@ -1403,7 +1438,8 @@ LP1_UNROLL
             if (coll) {
               rw = p.reward_collision;
               r.flags |= CA_IN_COLLISION;
-            } else if (hits_wall(k.map, r.px, r.py, r.rad)) {  // env.py:425-429, :494-506
+            } else if (wall_set ? hits_wall_in(k.map, wall_bits, r.px, r.py, r.rad)
+                                : hits_wall(k.map, r.px, r.py, r.rad)) {  // env.py:425-429, :494-506
               rw = p.reward_collision_wall;
               r.flags |= CA_IN_COLLISION;
             } else {
@@ -1488,6 +1524,8 @@ LP1_UNROLL
                                                    static_cast<unsigned>(reset_cnt), static_cast<unsigned>(a));
             }
             reset_lane(r, k.table + (c * N + a) * 6, k.heading_seed != 0, h0, p);
+            // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by its agent 0 lane
+            if (!MULTI && k.map_seed && a == 0) k.env_map[e] = map_draw(k.map_seed, k.env_id_offset + e, reset_cnt, k.num_maps);
             ep_step = 0;
             statics_dirty = true;
             if (RO) {
@@ -2087,11 +2125,21 @@ int cagpu_reset(const CaParams* p, const CaState* s, const CaOut* o, const doubl
   return launch_any(k, stream);
 }
 
+// the argument checks of the map-set entry points (CaMapSet)
+static int check_map_set(const CaMapSet* set, const char* who) {
+  if (!set || !set->env_map || !set->map.static_bits || set->num_maps < 1)
+    return fail(CA_EINVAL, "%s: NULL CaMapSet, env_map or static_bits, or num_maps < 1", who);
+  const CaMap& m = set->map;
+  if (m.rows < 1 || m.cols < 1 || !(m.cell > 0.0)) return fail(CA_EINVAL, "%s: bad CaMapSet geometry", who);
+  return CA_OK;
+}
+
 static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const double* ext, const CaAutoReset* ar,
                      int32_t n_steps, void* stream, const CaMap* map = nullptr, const bool ring = false,
-                     const int64_t snapshot_delta = 0, const bool query_snapshot = false) {
+                     const int64_t snapshot_delta = 0, const bool query_snapshot = false, const CaMapSet* set = nullptr) {
   int rc = check_params(p, s, o);
   if (rc) return rc;
+  if (set && (rc = check_map_set(set, "cagpu_step_maps"))) return rc;
   if (n_steps < 1) return fail(CA_EINVAL, "cagpu: n_steps must be >= 1%s");
   if ((n_steps > 1 || ring) && (s->rvo_collab || s->rvo_heading_noise || s->ext_state))
     return fail(CA_EINVAL, "cagpu: CaState.rvo_collab / rvo_heading_noise / ext_state are inputs of ONE step (the caller draws / "
@@ -2109,6 +2157,13 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
   if (map && map->static_bits) {
     if (map->rows < 1 || map->cols < 1 || !(map->cell > 0.0)) return fail(CA_EINVAL, "cagpu: bad CaMap%s");
     k.map = *map;
+  }
+  if (set) {  // (single step: the n-step kernels take no set)
+    k.map = set->map;
+    k.env_map = set->env_map;
+    k.map_words = static_cast<int64_t>(set->map.rows) * ((set->map.cols + 31) / 32);
+    k.num_maps = set->num_maps;
+    k.map_seed = ar ? set->map_seed : 0;  // (draws happen at auto-resets only)
   }
   k.n_steps = n_steps; k.mode = MODE_STEP;
   k.inv_rvo_dt = 1.0 / p->rvo_dt;
@@ -2148,7 +2203,14 @@ int cagpu_step_map(const CaParams* p, const CaState* s, const CaOut* o, const do
   return step_impl(p, s, o, ext_actions, ar, 1, stream, map);
 }
 
-int cagpu_laserscan(const CaParams* p, const CaState* s, const CaMap* map, const CaScan* scan, void* stream) {
+int cagpu_step_maps(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
+                    const CaMapSet* set, void* stream) {
+  if (!set) return fail(CA_EINVAL, "cagpu_step_maps: NULL CaMapSet%s");
+  return step_impl(p, s, o, ext_actions, ar, 1, stream, nullptr, false, 0, false, set);
+}
+
+static int laserscan_impl(const CaParams* p, const CaState* s, const CaMap* map, const CaScan* scan, void* stream,
+                          const CaMapSet* set = nullptr) {
   if (!p || !s || !map || !scan) return fail(CA_EINVAL, "cagpu_laserscan: NULL argument%s");
   if (p->num_envs < 1 || p->num_agents < 1 || p->num_agents > 256) return fail(CA_EINVAL, "cagpu_laserscan: bad sizes%s");
   if (map->rows < 1 || map->cols < 1 || !(map->cell > 0.0)) return fail(CA_EINVAL, "cagpu_laserscan: bad CaMap%s");
@@ -2161,6 +2223,7 @@ int cagpu_laserscan(const CaParams* p, const CaState* s, const CaMap* map, const
   ScanArgs k;
   std::memset(&k, 0, sizeof(k));
   k.p = *p; k.s = *s; k.m = *map; k.sc = *scan;
+  if (set) { k.env_map = set->env_map; k.num_maps = set->num_maps; }
   const int N = p->num_agents;
   const size_t total = align16(scan_grid_words(map->rows, map->cols) * 4) + static_cast<size_t>(N) * (4 * 8 + 2 * 8 + 3 * 4 + 2 * 8 + 2 * 8 + 3 * 4 + 4 * 4) +
                        static_cast<size_t>(scan->num_beams) * 16 + 256 * 4 + 32 + static_cast<size_t>(HIST_AG) * SCAN_NT;
@@ -2175,6 +2238,16 @@ int cagpu_laserscan(const CaParams* p, const CaState* s, const CaMap* map, const
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
   return CA_OK;
+}
+
+int cagpu_laserscan(const CaParams* p, const CaState* s, const CaMap* map, const CaScan* scan, void* stream) {
+  return laserscan_impl(p, s, map, scan, stream);
+}
+
+int cagpu_laserscan_maps(const CaParams* p, const CaState* s, const CaMapSet* set, const CaScan* scan, void* stream) {
+  const int rc = check_map_set(set, "cagpu_laserscan_maps");
+  if (rc) return rc;
+  return laserscan_impl(p, s, &set->map, scan, stream, set);
 }
 
 int cagpu_ga3c(const CaParams* p, const CaState* s, const float* obs, const CaNet* net, double* ext_actions, float* logits,

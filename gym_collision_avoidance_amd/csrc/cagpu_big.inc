@@ -81,6 +81,9 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
       }
     }
 
+    // a map set: this env's grid for the wall tests of this step (one index per env: the workgroup holds the env)
+    const uint32_t* wall_bits = k.map.static_bits;
+    if (k.env_map && k.mode == MODE_STEP) wall_bits = set_grid(wall_bits, k.map_words, k.num_maps, k.env_map[e], a == 0);
     if (k.mode == MODE_STEP) {
       // ================= A1: float bodies (RVOPolicy.py:57-74); an absent slot sits at infinity
       const uint32_t pol = (r.flags >> CA_POLICY_SHIFT) & 0xF;
@@ -245,7 +248,7 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
           if (coll) {
             rw = p.reward_collision;
             r.flags |= CA_IN_COLLISION;
-          } else if (hits_wall(k.map, r.px, r.py, r.rad)) {  // env.py:425-429, :494-506
+          } else if (hits_wall_in(k.map, wall_bits, r.px, r.py, r.rad)) {  // env.py:425-429, :494-506
             rw = p.reward_collision_wall;
             r.flags |= CA_IN_COLLISION;
           } else {
@@ -371,6 +374,8 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
         st[7] += extra;
       }
       reset_cnt += 1;
+      // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by agent 0's thread
+      if (k.map_seed && a == 0) k.env_map[e] = map_draw(k.map_seed, k.env_id_offset + e, reset_cnt, k.num_maps);
       if (active) {
         const long c = (k.env_id_offset + e + static_cast<long>(reset_cnt) * k.case_stride) % k.n_cases;
         double h0 = 0.0;

@@ -737,6 +737,15 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
       }
       // Agent.turning_dir (UnicycleDynamics.py:41-47)
       if (k.s.turning_dir && turned) sh_td[lane] = turning_dir_next(sh_td[lane], heading);
+      // a map set (single-step kernel only; uniform test): the env's grid for the wall tests of A3, its index read by the
+      // env's agent 0 lane (before the wait, which hides the load) and handed to the others
+      const bool wall_set = !MULTI && k.env_map != nullptr;
+      const uint32_t* wall_bits = nullptr;
+      if (wall_set) {
+        int m = (active && a == 0) ? k.env_map[env0 + le] : 0;
+        m = __shfl(m, ebase);
+        wall_bits = active ? set_grid(k.map.static_bits, k.map_words, k.num_maps, m, a == 0) : nullptr;
+      }
       wait_for(&sh_misc[M_CP3], 3);  // P3 done (the three S-pair waves)
       PT(6);
       // ================= A3: rewards + collision flag (env.py:394-456), observation scalars
@@ -756,7 +765,8 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
           if (coll) {
             rw = p.reward_collision;
             flags |= CA_IN_COLLISION;
-          } else if (hits_wall(k.map, px, py, rad)) {  // env.py:425-429, :494-506
+          } else if (wall_set ? hits_wall_in(k.map, wall_bits, px, py, rad)
+                              : hits_wall(k.map, px, py, rad)) {  // env.py:425-429, :494-506
             rw = p.reward_collision_wall;
             flags |= CA_IN_COLLISION;
           } else {
@@ -833,6 +843,8 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
             Lane r;
             r.flags = flags;
             reset_lane(r, k.table + (c * N + a) * 6, false, 0.0, p);
+            // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by its agent 0 lane
+            if (!MULTI && k.map_seed && a == 0) k.env_map[env0 + le] = map_draw(k.map_seed, k.env_id_offset + env0 + le, reset_cnt, k.num_maps);
             px = r.px; py = r.py; vx = r.vx; vy = r.vy; heading = r.heading;
             act0 = r.act0; act1 = r.act1; flags = r.flags; step_num = r.step_num;
             sh_gx[lane] = r.gx; sh_gy[lane] = r.gy; sh_ps[lane] = r.ps; sh_rad[lane] = r.rad;

@@ -16,6 +16,9 @@ struct ScanArgs {
   CaState s;
   CaMap m;
   CaScan sc;
+  // map set (cagpu_laserscan_maps; nullptr otherwise): env e scans grid env_map[e] of the num_maps grids at m.static_bits
+  const int32_t* env_map;
+  int32_t num_maps;
 };
 
 // floor(origin + sign * coord / cell) exactly as float64 numpy computes it
@@ -32,10 +35,11 @@ __device__ __forceinline__ bool grid_bit(const uint32_t* g, int wpr, long r, lon
   return (g[r * wpr + (c >> 5)] >> (c & 31)) & 1u;
 }
 
-// collision_avoidance_env.py:494-506 + Map.py:54-58: does the agent's disc cover an occupied STATIC cell?
+// collision_avoidance_env.py:494-506 + Map.py:54-58: does the agent's disc cover an occupied STATIC cell of the grid
+// `bits` (m's geometry; nullptr: no walls)?
 template <typename MapT>  // (CaMap, or an address-space-qualified view of it)
-__device__ bool hits_wall(const MapT& m, double x, double y, double radius) {
-  if (!m.static_bits) return false;
+__device__ bool hits_wall_in(const MapT& m, const uint32_t* bits, double x, double y, double radius) {
+  if (!bits) return false;
   const double fr = floor(m.origin_r - y / m.cell), fc = floor(m.origin_c + x / m.cell);
   if (!(fr >= 0.0 && fc >= 0.0 && fr < m.rows && fc < m.cols)) return false;
   const int gr = static_cast<int>(fr), gc = static_cast<int>(fc);  // (32-bit loop state: this sits inside the agent wave)
@@ -48,10 +52,15 @@ __device__ bool hits_wall(const MapT& m, double x, double y, double radius) {
     const double fdr = static_cast<double>(r - gr);
     for (int c = c_lo; c <= c_hi; ++c) {
       const double fdc = static_cast<double>(c - gc);
-      if (fdc * fdc + fdr * fdr < rr && grid_bit(m.static_bits, wpr, r, c)) return true;
+      if (fdc * fdc + fdr * fdr < rr && grid_bit(bits, wpr, r, c)) return true;
     }
   }
   return false;
+}
+// ... of the single map
+template <typename MapT>
+__device__ bool hits_wall(const MapT& m, double x, double y, double radius) {
+  return hits_wall_in(m, m.static_bits, x, y, radius);
 }
 
 constexpr int SCAN_NT = 512;
@@ -122,15 +131,17 @@ __global__ __launch_bounds__(SCAN_NT) void scan_kernel(const ScanArgs k) {
   const double reach = (k.sc.num_ranges - 1) * k.sc.range_res, res_cells = k.sc.range_res * inv_cell;
 
   // 1a. static grid -> padded LDS byte grid (cell (r, c) lands at byte (r + PAD) * pitch + c + PAD), four cells per
-  // store; per-agent cells
+  // store; per-agent cells.  A map set: this env's own grid (one index per workgroup).
   {
+    const uint32_t* sbits = k.m.static_bits;
+    if (k.env_map) sbits = set_grid(sbits, static_cast<long>(rows) * wpr, k.num_maps, k.env_map[e], tid == 0);
     const int p4 = pitch >> 2;
     for (int w = tid; w < static_cast<int>(scan_grid_words(rows, cols)); w += SCAN_NT) {
       const int pr = w / p4, c0 = (w - pr * p4) * 4 - SCAN_PAD;  // first of this word's four cells
       const int r = pr - SCAN_PAD;
       uint32_t v = 0u;
-      if (k.m.static_bits && r >= 0 && r < rows) {
-        const uint32_t* src = k.m.static_bits + static_cast<long>(r) * wpr;
+      if (sbits && r >= 0 && r < rows) {
+        const uint32_t* src = sbits + static_cast<long>(r) * wpr;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int c = c0 + u;

@@ -118,6 +118,9 @@ class CollisionAvoidanceEnv(Env):
         self.prev_episode_agents = None
         self.static_map_filename = None
         self.map = None
+        self._map_set = None      # set_static_map(..., per_env=True)
+        self.maps = None          # ... one Map per entry of the set
+        self.map_index = None     # ... the device int32 [E] map of every env
         self.episode_step_number = None
         self.episode_number = 0
         self.plot_save_dir = None
@@ -174,11 +177,36 @@ class CollisionAvoidanceEnv(Env):
                              case_stride=self.num_envs if case_stride is None else case_stride)
         self.default_agents = None
 
-    def set_static_map(self, static_map):
+    def set_static_map(self, static_map, per_env=False, map_seed=None):
         """The static obstacles used when Config.USE_STATIC_MAP (collision_avoidance_env.py:369-392): the path of a
         binary image file like the reference takes (or a list of paths, one drawn per episode), OR the occupancy grid
         itself as a bool array [160, 160] (True = occupied; row = floor(80 - y/0.1), col = floor(80 + x/0.1),
-        Map.py:26-32), or None for an empty map."""
+        Map.py:26-32), or None for an empty map.
+
+        per_env=True: a MAP SET -- `static_map` is a list of image paths, a list of bool grids or an array [M, 160, 160],
+        and every env runs its own map: at every reset() each env draws one with np.random (as the reference draws its
+        one map, :384-385), and every on-device auto-reset draws the env's next one (core.BatchedSim.set_map).  The
+        device draws are keyed by a number that reset() takes from np.random (map_seed None: seeding numpy makes a run
+        reproducible) or from a generator seeded with map_seed.  `maps` then holds one Map per entry, `map_index` the
+        device int32 [E] map of every env, and `map` still the map of env 0.  Without per_env the behaviour is the
+        single-map one above (a list of paths: one draw per reset for the whole batch)."""
+        self._map_set = None
+        if per_env:
+            entries = list(static_map) if isinstance(static_map, (list, tuple)) else list(np.asarray(static_map))
+            if not entries:
+                raise ValueError("set_static_map(per_env=True) needs at least one map")
+            maps = []
+            for m in entries:
+                if isinstance(m, str):
+                    maps.append(Map(16, 16, 0.1, map_filename=m))
+                    continue
+                grid = np.asarray(m)
+                if grid.shape != (160, 160):
+                    raise ValueError("a map of the set has shape %s, expected (160, 160) (Map(16 m, 16 m, 0.1 m))" % (grid.shape,))
+                maps.append(Map(16, 16, 0.1, static_map=grid.astype(bool)))
+            self._map_set = dict(maps=maps, rng=None if map_seed is None else
+                                 np.random.Generator(np.random.PCG64(int(map_seed) & 0xFFFFFFFFFFFFFFFF)))
+            self.maps = maps
         self.static_map_filename = static_map
 
     def set_plot_save_dir(self, plot_save_dir):
@@ -506,7 +534,21 @@ class CollisionAvoidanceEnv(Env):
         self._la_dt_ok = sim.p.dt == self.dt_nominal
         if self._la_on:
             self._learning_info = {a.id: a.policy.is_still_learning for a in self.agents}
-        if Config.USE_STATIC_MAP:  # collision_avoidance_env.py:273-274, :378-392: Map(16 m, 16 m, 0.1 m)
+        if Config.USE_STATIC_MAP and self._map_set is not None:
+            # a map set: every env draws its own map (collision_avoidance_env.py:384-385, once per env), the auto-resets
+            # draw on the device under a key taken here
+            maps = self._map_set["maps"]
+            idx = np.random.randint(len(maps), size=E)
+            rng = self._map_set["rng"]
+            key = int(rng.integers(1, 1 << 64, dtype=np.uint64)) if rng is not None else \
+                int(np.random.randint(1, np.iinfo(np.int64).max, dtype=np.int64))
+            sim.set_map(np.stack([m.static_map for m in maps]), num_beams=Config.LASERSCAN_LENGTH,
+                        num_to_store=Config.LASERSCAN_NUM_PAST, env_map=idx)
+            sim.set_map_seed(key)
+            self.map = maps[int(idx[0])]
+            self.map_index = sim.env_map
+            sim.laserscan()
+        elif Config.USE_STATIC_MAP:  # collision_avoidance_env.py:273-274, :378-392: Map(16 m, 16 m, 0.1 m)
             sm = self.static_map_filename
             if isinstance(sm, list) and sm and isinstance(sm[0], str):
                 sm = np.random.choice(sm)  # collision_avoidance_env.py:384-385

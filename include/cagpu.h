@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CAGPU_VERSION 11
+#define CAGPU_VERSION 12
 
 /* error codes */
 enum { CA_OK = 0, CA_EINVAL = -1, CA_EUNSUPPORTED = -2, CA_ELAUNCH = -3, CA_ENODEVICE = -4 };
@@ -210,6 +210,22 @@ typedef struct CaMap {
   double cell, origin_r, origin_c;
 } CaMap;
 
+/* A MAP SET (v12): M static grids of one geometry and a map per env -- the batched form of the reference's list of
+ * candidate maps, one of which env.reset() draws for every episode (collision_avoidance_env.py:369-376, :274-275,
+ * :384-385).  map.static_bits holds the M grids back to back, grid m at word m * rows * ((cols + 31) / 32), each laid out
+ * as a CaMap grid.  An env whose env_map entry lies outside [0, num_maps) reads no map memory (it sees an empty map) and
+ * raises bit 2 of the device fault word (cagpu_device_faults). */
+typedef struct CaMapSet {
+  CaMap map;           /* the geometry every map shares; static_bits = the num_maps grids (must not be NULL) */
+  int32_t *env_map;    /* device int32 [E]: the map of env e.  STATE: rewritten by an auto-reset when map_seed != 0 */
+  int32_t num_maps, reserved0;
+  uint64_t map_seed;   /* 0: an auto-reset keeps the env's map.  Otherwise the k-th auto-reset of env e sets
+                          env_map[e] = min(floor(M * u), M - 1), u = the Philox4x32-10 uniform of key map_seed and counter
+                          (g lo, g hi, k, 0xFFFFFFFF), g = CaAutoReset.env_id_offset + e (the construction of heading_seed's
+                          draws, whose last counter word is an agent index < 1024: the two streams never meet) -- a pure
+                          function of (map_seed, global env id, reset count), whatever the batch size or sharding. */
+} CaMapSet;
+
 /* LaserScanSensor state + observation (sensors/LaserScanSensor.py:24-44): num_beams beams over
  * [min_angle, max_angle] around the heading, num_ranges samples every range_res metres. */
 typedef struct CaScan {
@@ -285,6 +301,16 @@ int cagpu_step_map(const CaParams *p, const CaState *s, const CaOut *o, const do
  * `cumsum == 1` indexing, LaserScanSensor.py:77-81).  An agent with step_num == 0 takes its first measurement (all
  * history rows filled, :84-85), otherwise the history is rolled (:86-88). */
 int cagpu_laserscan(const CaParams *p, const CaState *s, const CaMap *map, const CaScan *scan, void *stream);
+
+/* cagpu_step_map / cagpu_laserscan with a map set (v12): every env tests its walls against, and scans, its OWN map
+ * env_map[e].  With set->map_seed != 0 an auto-reset draws the env's next map (CaMapSet.map_seed); the wall test of the
+ * terminal step still uses the old map, the next step and the next scan the new one (the reference's reset observation
+ * already sees the new map).  CA_EINVAL, nothing launched: set, set->env_map or set->map.static_bits NULL,
+ * num_maps < 1, or a bad geometry.  Envs with more than 64 agents, the pipelined and the plain step kernels all take a
+ * set; cagpu_rollout / cagpu_rollout_ring do not. */
+int cagpu_step_maps(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
+                    const CaMapSet *set, void *stream);
+int cagpu_laserscan_maps(const CaParams *p, const CaState *s, const CaMapSet *set, const CaScan *scan, void *stream);
 
 /* Replaces: GA3CCADRLPolicy.find_next_action (policies/GA3CCADRLPolicy.py:49-84) + NetworkVPCore.predict_p
  * (GA3C_CADRL/network.py:24-41, the TF1 graph of the checkpoint) for every agent whose policy is CA_POL_GA3C_CADRL and
@@ -403,6 +429,8 @@ uint64_t cagpu_workspace_bytes(const CaParams *p);
  * bit 1 = an operand of the GA3C-CADRL network kernel left the range of its two-plane fp16 split (|x| >= 65504: a normalised
  * input or an activation; csrc/cagpu_ga3c.inc), i.e. some cagpu_ga3c call since the last clear chose its actions from
  * saturated values.
+ * bit 2 = a map-set env's map index (CaMapSet.env_map) lay outside [0, num_maps) (cagpu_step_maps / cagpu_laserscan_maps,
+ * v12): that env saw an empty map in some call since the last clear.
  * *faults receives the word; clear != 0 resets it.  0 in normal operation; check it wherever the host synchronises anyway. */
 int cagpu_device_faults(uint32_t *faults, int32_t clear);
 
