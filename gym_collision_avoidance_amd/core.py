@@ -130,6 +130,9 @@ class BatchedSim(object):
         self.env_map = None
         self._scan = None
         self.scan = None
+        self.occ = None           # OccupancyGridSensor windows (set_occupancy_grid): bool [E, N, H, W] / None
+        self.occ_bits = None      # ... bit-packed: int32 [E, N, H, (W + 31) // 32] / None
+        self._occ = None
         self.ga3c_fused = False   # cagpu_ga3c with obs = NULL: sensing fused into the network kernel (see ga3c())
         self._net = None          # GA3C-CADRL weights (load_ga3c); _nets: {checkpoint index: (CaNet, tensors)}
         self._net_tensors = None
@@ -494,6 +497,7 @@ class BatchedSim(object):
         bits = None
         self._fast_args = None
         self._maps, self._map_rng, self.env_map = None, None, None
+        self.occ, self.occ_bits, self._occ = None, None, None   # (sized by the map's cell: set_occupancy_grid() again)
         M = 0
         if static_map is not None:
             m = np.asarray(static_map).astype(bool)
@@ -564,6 +568,42 @@ class BatchedSim(object):
             nat.check(self.lib.cagpu_laserscan(C.byref(self.p), C.byref(self._cs), C.byref(self._map),
                                                C.byref(self._scan), self._stream()))
         return self.scan
+
+    def set_occupancy_grid(self, x_width=5., y_width=5., packed=False):
+        """Buffers of the OccupancyGridSensor (reference sensors/OccupancyGridSensor.py): every agent's window of
+        y_width x x_width metres around it, H = int(y_width / cell) rows x W = int(x_width / cell) columns of the map
+        given to set_map() (call that first; calling it again drops these buffers).  `self.occ`: bool [E, N, H, W];
+        packed=True: `self.occ_bits` instead, int32 [E, N, H, (W + 31) // 32], cell b of a row = bit b & 31 of word b >> 5
+        (1/6 of the bytes at W = 50); packed="both": both."""
+        assert self._map is not None, "set_map() first"
+        self.sync()
+        cell = float(self._map.cell)
+        H, W = int(y_width / cell), int(x_width / cell)
+        if not (1 <= H <= 256 and 1 <= W <= 256):
+            raise ValueError("occupancy grid of %d x %d cells: height and width must be in [1, 256]" % (H, W))
+        self.occ, self.occ_bits = None, None
+        if packed != True:  # noqa: E712 -- False or "both"
+            self._occ_cells = torch.zeros((self.E, self.N, H, W), dtype=torch.uint8, device=self.device)
+            self.occ = self._occ_cells.view(torch.bool)   # (0 / 1 bytes: no conversion kernel)
+        if packed:
+            self.occ_bits = torch.zeros((self.E, self.N, H, (W + 31) // 32), dtype=torch.int32, device=self.device)
+        self._occ = nat.CaOccGrid(cells=None if self.occ is None else self._occ_cells.data_ptr(),
+                                  bits=None if self.occ_bits is None else self.occ_bits.data_ptr(), height=H, width=W,
+                                  x_width=float(x_width), y_width=float(y_width))
+
+    def occupancy_grid(self):
+        """'occupancy_grid' observation of the current state (call after reset / step): `self.occ` (bool [E,N,H,W]), or
+        `self.occ_bits` where set_occupancy_grid(packed=True) asked for the packed form only.  A pure function of the
+        state and the env's current map (cagpu_occupancy_grid / _maps, csrc/cagpu_occ.inc)."""
+        assert self._occ is not None, "set_occupancy_grid() first"
+        self.sync()
+        if self._maps is not None:
+            nat.check(self.lib.cagpu_occupancy_grid_maps(C.byref(self.p), C.byref(self._cs), C.byref(self._maps),
+                                                         C.byref(self._occ), self._stream()))
+        else:
+            nat.check(self.lib.cagpu_occupancy_grid(C.byref(self.p), C.byref(self._cs), C.byref(self._map),
+                                                    C.byref(self._occ), self._stream()))
+        return self.occ if self.occ is not None else self.occ_bits
 
     def _new_outputs(self, keep=False):
         """keep: the new tensors start as copies of the current ones (a masked reset rewrites only some envs' rows)"""

@@ -588,6 +588,7 @@ __device__ unsigned long long g_wgtime[4096 * 8];
 
 __host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
 #include "cagpu_scan.inc"
+#include "cagpu_occ.inc"
 #include "cagpu_ga3c.inc"
 #include "cagpu_gen.inc"
 
@@ -2248,6 +2249,46 @@ int cagpu_laserscan_maps(const CaParams* p, const CaState* s, const CaMapSet* se
   const int rc = check_map_set(set, "cagpu_laserscan_maps");
   if (rc) return rc;
   return laserscan_impl(p, s, &set->map, scan, stream, set);
+}
+
+static int occupancy_impl(const CaParams* p, const CaState* s, const CaMap* map, const CaOccGrid* g, void* stream,
+                          const CaMapSet* set = nullptr) {
+  if (!p || !s || !map || !g) return fail(CA_EINVAL, "cagpu_occupancy_grid: NULL argument%s");
+  if (p->num_envs < 1 || p->num_agents < 1 || p->num_agents > big::NT_MAX) return fail(CA_EINVAL, "cagpu_occupancy_grid: bad sizes%s");
+  if (map->rows < 1 || map->cols < 1 || !(map->cell > 0.0)) return fail(CA_EINVAL, "cagpu_occupancy_grid: bad CaMap%s");
+  if (!g->cells && !g->bits) return fail(CA_EINVAL, "cagpu_occupancy_grid: CaOccGrid.cells and .bits are both NULL%s");
+  if (g->height < 1 || g->height > 256 || g->width < 1 || g->width > 256)
+    return fail(CA_EINVAL, "cagpu_occupancy_grid: height and width must be in [1, 256]%s");
+  if ((reinterpret_cast<uintptr_t>(g->cells) | reinterpret_cast<uintptr_t>(g->bits)) & 15)
+    return fail(CA_EINVAL, "cagpu_occupancy_grid: output pointers must be 16-byte aligned%s");
+  if (!s->pos_x || !s->pos_y || !s->radius) return fail(CA_EINVAL, "cagpu_occupancy_grid: NULL state pointer%s");
+  const size_t bitmap = static_cast<size_t>(map->rows) * ((static_cast<size_t>(map->cols) + 31) / 32) * 4;
+  if (bitmap > 128 * 1024) return fail(CA_EUNSUPPORTED, "cagpu_occupancy_grid: map too large for the LDS bitmap%s");
+  OccArgs k;
+  std::memset(&k, 0, sizeof(k));
+  k.p = *p; k.s = *s; k.m = *map; k.g = *g;
+  if (set) { k.env_map = set->env_map; k.num_maps = set->num_maps; }
+  const size_t total = occ_lds_bytes(map->rows, map->cols, p->num_agents);
+  if (total > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&occ_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(total));
+    if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: hipFuncSetAttribute: %s", hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(occ_kernel, dim3(static_cast<unsigned>(p->num_envs)), dim3(OCC_NT), total,
+                     static_cast<hipStream_t>(stream), k);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
+}
+
+int cagpu_occupancy_grid(const CaParams* p, const CaState* s, const CaMap* map, const CaOccGrid* g, void* stream) {
+  return occupancy_impl(p, s, map, g, stream);
+}
+
+int cagpu_occupancy_grid_maps(const CaParams* p, const CaState* s, const CaMapSet* set, const CaOccGrid* g, void* stream) {
+  const int rc = check_map_set(set, "cagpu_occupancy_grid_maps");
+  if (rc) return rc;
+  return occupancy_impl(p, s, &set->map, g, stream, set);
 }
 
 int cagpu_ga3c(const CaParams* p, const CaState* s, const float* obs, const CaNet* net, double* ext_actions, float* logits,

@@ -14,3 +14,11 @@ _spec.loader.exec_module(_mod)
 _cls = getattr(_mod, gym_config_class, None)
 assert callable(_cls), "config class %r not found in %s" % (gym_config_class, gym_config_path)
 Config = _cls()
+
+# The sensor registry (`test_cases.sensor_dict`, reference test_cases.py:56-66) is completed here, once Config exists:
+# OccupancyGridSensor joins it under "occupancy_grid", so that every way of importing `envs.test_cases` (the parent
+# package runs first) finds the three sensors of the reference registered.
+from gym_collision_avoidance_amd.envs import test_cases as _test_cases  # noqa: E402
+from gym_collision_avoidance_amd.envs.sensors.OccupancyGridSensor import OccupancyGridSensor as _OccupancyGridSensor  # noqa: E402
+
+_test_cases.sensor_dict.setdefault("occupancy_grid", _OccupancyGridSensor)

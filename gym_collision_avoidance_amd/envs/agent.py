@@ -173,6 +173,8 @@ class Agent(object):
         data = {"other_agents_states": oa}
         if self._env is not None and self._env._sim is not None and self._env._sim.scan is not None:
             data["laserscan"] = self._env._scan_host()[self._e, self._a].astype(np.float64)
+        if self._env is not None and self._env._sim is not None and self._env._sim.occ is not None:
+            data["occupancy_grid"] = self._env._occ_host()[self._e, self._a].copy()
         return data
 
     def get_sensor_data(self, sensor_name):
@@ -195,7 +197,8 @@ class Agent(object):
                    "pref_speed": lambda: self.pref_speed, "radius": lambda: self.radius,
                    "other_agent_states": lambda: self.other_agent_states,
                    "other_agents_states": lambda: self.get_sensor_data("other_agents_states"),
-                   "laserscan": lambda: self.get_sensor_data("laserscan")}
+                   "laserscan": lambda: self.get_sensor_data("laserscan"),
+                   "occupancy_grid": lambda: self.get_sensor_data("occupancy_grid")}
         return {s: np.array(getters[s]()) for s in Config.STATES_IN_OBS}
 
     def sense(self, agents, agent_index, top_down_map):

@@ -132,6 +132,7 @@ class CollisionAvoidanceEnv(Env):
         self._snap = None
         self._obs_np = None
         self._scan_np = None
+        self._occ_np = None
         self._fixture = None
         self._all_agents = None
         self._host_policies, self._host_by_env, self._groups = [], None, []
@@ -146,7 +147,7 @@ class CollisionAvoidanceEnv(Env):
 
     def set_fixture_suite(self, num_agents, policies="RVO", agents_dynamics="unicycle", auto_reset=True,
                           env_id_offset=0, case_stride=None, table=None, generate=None, random_headings=None,
-                          heading_seed=1):
+                          heading_seed=1, agents_sensors=("other_agents_states",)):
         """Batched evaluation on the reference's 500-case suite (run_full_test_suite.py:54-130): env e starts on case
         (env_id_offset + e) % 500 and, with auto_reset, its k-th episode loads case (env_id_offset + e + k*stride) % 500
         on the device (DummyVecEnv semantics, vec_env.py:120-128).
@@ -160,7 +161,9 @@ class CollisionAvoidanceEnv(Env):
         a ragged table whose short cases leave their last slots empty.
         `random_headings` (default: `not Config.EVALUATE_MODE`, the reference's rule, test_cases.py:553-559): initial
         headings -- at reset() and at every on-device auto-reset -- are uniform in [-pi, pi) instead of pointing at the
-        goal; drawn on the device from `heading_seed`."""
+        goal; drawn on the device from `heading_seed`.
+        `agents_sensors`: the sensor names (test_cases.sensor_dict) of every agent, e.g. ("other_agents_states",
+        "laserscan", "occupancy_grid") under Config.USE_STATIC_MAP."""
         if generate is not None:
             assert table is None and int(generate["num_cases"]) >= 1 and "seed" in generate
             table = None
@@ -172,6 +175,7 @@ class CollisionAvoidanceEnv(Env):
             assert table.ndim == 3 and tuple(table.shape[1:]) == (num_agents, 6), table.shape
         self._fixture = dict(table=table, policies=policies, dynamics=agents_dynamics, auto_reset=auto_reset,
                              env_id_offset=env_id_offset, num_agents=num_agents, generate=generate,
+                             sensors=tuple(agents_sensors),
                              heading_seed=(int(heading_seed) or 1) if (random_headings if random_headings is not None
                                                                       else not Config.EVALUATE_MODE) else 0,
                              case_stride=self.num_envs if case_stride is None else case_stride)
@@ -262,7 +266,7 @@ class CollisionAvoidanceEnv(Env):
         sim.step(ext, ext_state=self._ext_state)
         self._snap, self._obs_np, self._scan_np = None, None, None
         if Config.USE_STATIC_MAP:
-            sim.laserscan()
+            self._map_sensors()
         if Config.STORE_HISTORY and self.num_envs == 1:
             self._record_history()
         if self.num_envs > 1:
@@ -301,7 +305,8 @@ class CollisionAvoidanceEnv(Env):
             row0 = f["table"][idx]
             row0 = row0.cpu().numpy() if hasattr(row0, "cpu") else row0
             row0 = row0[row0[:, 5] > 0]   # (a ragged table pads short cases with radius-0 rows: empty slots)
-            self.agents = tc.cadrl_test_case_to_agents(row0, policies=f["policies"], agents_dynamics=f["dynamics"])
+            self.agents = tc.cadrl_test_case_to_agents(row0, policies=f["policies"], agents_dynamics=f["dynamics"],
+                                                       agents_sensors=f["sensors"])
         else:
             if self.default_agents is None:
                 if E > 1:
@@ -547,7 +552,7 @@ class CollisionAvoidanceEnv(Env):
             sim.set_map_seed(key)
             self.map = maps[int(idx[0])]
             self.map_index = sim.env_map
-            sim.laserscan()
+            self._map_sensors(groups)
         elif Config.USE_STATIC_MAP:  # collision_avoidance_env.py:273-274, :378-392: Map(16 m, 16 m, 0.1 m)
             sm = self.static_map_filename
             if isinstance(sm, list) and sm and isinstance(sm[0], str):
@@ -555,7 +560,7 @@ class CollisionAvoidanceEnv(Env):
             self.map = Map(16, 16, 0.1, map_filename=sm) if isinstance(sm, str) else Map(16, 16, 0.1, static_map=sm)
             sim.set_map(self.map.static_map if self.map.static_map.any() else None, num_beams=Config.LASERSCAN_LENGTH,
                         num_to_store=Config.LASERSCAN_NUM_PAST)
-            sim.laserscan()
+            self._map_sensors(groups)
         if Config.STORE_HISTORY and E == 1:
             self._record_history(initial=True)
 
@@ -659,6 +664,31 @@ class CollisionAvoidanceEnv(Env):
             self._scan_np = self._sim.scan.cpu().numpy()
         return self._scan_np
 
+    def _map_sensors(self, groups=None):
+        """the map sensors of the current state: the laser scan, and the OccupancyGridSensor windows where some agent of
+        the batch lists that sensor.  `groups` (the reset upload, right after set_map()): the batch's agent lists, from
+        which the window size is taken -- the windows are ONE tensor [E, N, H, W], so every agent must agree on it."""
+        sim = self._sim
+        if groups is not None:
+            from .sensors.OccupancyGridSensor import OccupancyGridSensor
+            sizes = {(float(s.x_width), float(s.y_width)) for g in groups for a in g for s in a.sensors
+                     if isinstance(s, OccupancyGridSensor)}
+            if len(sizes) > 1:
+                raise ValueError("OccupancyGridSensor: the agents of a batch must agree on x_width / y_width "
+                                 "(one window tensor per batch), got %s" % sorted(sizes))
+            if sizes:
+                (xw, yw), = sizes
+                sim.set_occupancy_grid(x_width=xw, y_width=yw)
+        sim.laserscan()
+        self._occ_np = None
+        if sim.occ is not None:
+            sim.occupancy_grid()
+
+    def _occ_host(self):
+        if self._occ_np is None:
+            self._occ_np = self._sim.occ.cpu().numpy()
+        return self._occ_np
+
     def _write_agent(self, e, a, **fields):
         for name, v in fields.items():
             self._sim.state[name][e, a] = float(v)   # (`state` rewinds a look-ahead ring to the step last handed out)
@@ -695,6 +725,10 @@ class CollisionAvoidanceEnv(Env):
                 obs[s] = r[6:6 + 7 * K].astype(np.float64).reshape(K, 7)
             elif s == "laserscan":
                 obs[s] = self._scan_host()[e, i].astype(np.float64)
+            elif s == "occupancy_grid":
+                if self._sim.occ is None:
+                    raise RuntimeError("'occupancy_grid' is in Config.STATES_IN_OBS but no agent lists OccupancyGridSensor")
+                obs[s] = self._occ_host()[e, i].copy()
             elif s == "other_agent_states":
                 obs[s] = r[6:13].astype(np.float64)
             elif s == "is_learning":
@@ -738,6 +772,12 @@ class CollisionAvoidanceEnv(Env):
         """float32 device tensor [E, N, LASERSCAN_NUM_PAST, LASERSCAN_LENGTH] (Config.USE_STATIC_MAP only)."""
         return None if self._sim is None else self._sim.scan
 
+    @property
+    def occupancy_grid(self):
+        """bool device tensor [E, N, H, W]: every agent's OccupancyGridSensor window of the current state (H x W =
+        y_width x x_width in map cells); None unless some agent of the batch lists the sensor."""
+        return None if self._sim is None else self._sim.occ
+
     # ------------------------------------------------------------------ batched extras
     def rollout(self, n_steps):
         """n_steps x `step(None)` in ONE launch (`cagpu_rollout`): the device-side form of env_utils.run_episode's
@@ -756,7 +796,7 @@ class CollisionAvoidanceEnv(Env):
         sim.rollout(int(n_steps))
         self._snap, self._obs_np, self._scan_np = None, None, None
         if Config.USE_STATIC_MAP:
-            sim.laserscan()
+            self._map_sensors()
         info = {"which_agents_done": sim.done.bool() if self.num_envs > 1 else
                 {a.id: bool(d) for a, d in zip(self.agents, sim.done[0].cpu().numpy())},
                 "which_agents_learning": {a.id: a.policy.is_still_learning for a in self.agents}}

@@ -92,6 +92,7 @@ class Config(object):
                                           np.tile(oth_mean, (K, 1)), np.tile(oth_std, (K, 1))),
             "laserscan": _state(scan, [0., 6.], 'get_sensor_data("laserscan")',
                                 5. * np.ones(scan, np.float32), 5. * np.ones(scan, np.float32)),
+            "occupancy_grid": _state((50, 50), [0., 1.], 'get_sensor_data("occupancy_grid")'),
             "is_learning": _state(1, [0., 1.], 'get_agent_data_equiv("policy.str", "learning")'),
             "other_agents_states_encoded": _state(100., [0., 1.], 'get_sensor_data("other_agents_states_encoded")'),
         }

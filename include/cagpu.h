@@ -235,6 +235,18 @@ typedef struct CaScan {
   double min_angle, max_angle, range_res, max_range;
 } CaScan;
 
+/* OccupancyGridSensor window + outputs (sensors/OccupancyGridSensor.py:15-22, :44): every agent's height x width crop of
+ * its env's dynamic map, height = int(y_width / cell), width = int(x_width / cell) (the reference's 5 m x 5 m on the 0.1 m
+ * map: 50 x 50).  Two output formats, either pointer may be NULL, not both (device, 16-byte aligned):
+ *   cells  uint8  [E,N,height,width], 0 / 1 -- a bool array as the reference returns it;
+ *   bits   uint32 [E,N,height,(width + 31) / 32]: cell b of a window row is bit (b & 31) of word b >> 5, unused high bits 0. */
+typedef struct CaOccGrid {
+  uint8_t *cells;
+  uint32_t *bits;
+  int32_t height, width;   /* 1 .. 256 each */
+  double x_width, y_width; /* metres: the window spans [px - x_width / 2, px + x_width / 2) x (py - y_width / 2, py + y_width / 2] */
+} CaOccGrid;
+
 /* GA3C-CADRL network weights (policies/GA3C_CADRL/checkpoints/<run>/network_*.data-00000-of-00001): device float
  * pointers in the checkpoint's own layout, kernels row-major [in, out].  LSTM gate order i, j, f, o. */
 typedef struct CaNet {
@@ -311,6 +323,23 @@ int cagpu_laserscan(const CaParams *p, const CaState *s, const CaMap *map, const
 int cagpu_step_maps(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                     const CaMapSet *set, void *stream);
 int cagpu_laserscan_maps(const CaParams *p, const CaState *s, const CaMapSet *set, const CaScan *scan, void *stream);
+
+/* Replaces: Map.add_agents_to_map (Map.py:46-64) + OccupancyGridSensor.sense (sensors/OccupancyGridSensor.py:24-82) for every
+ * agent of every env, on the CURRENT state: the env's dynamic map -- the static grid OR a disc per agent slot around its
+ * floored cell, exactly the grid cagpu_laserscan marches through, except that the agent's OWN disc stays in -- is assembled as
+ * a bitmap in LDS and every agent's window is cropped from it.  ANCHORING RULE: the window's top-left map cell is
+ *   i0 = floor(origin_r - (py + y_width / 2) / cell),  j0 = floor(origin_c + (px - x_width / 2) / cell)
+ * (float64, true divisions: the reference's own upper-left corner), out[a, b] = map[i0 + a, j0 + b], 0 for cells outside the
+ * map.  DIVERGENCE: the reference computes both corners of the window independently and raises ValueError (a broadcast of
+ * 49 or 51 cells into 50) where their floors disagree about the span -- at some "round" positions such as px = -8.8 or
+ * py = 8.8 on the 16 m map; this call always returns height x width, identical to the reference wherever the reference
+ * returns.  Reads pos_x, pos_y, radius only and writes no simulator state: a pure function of the current state and the env's
+ * current map (nothing to do at a reset).  Any num_agents up to 1024.  CA_EINVAL, nothing launched: NULL arguments / state pointers, bad sizes, bad CaMap,
+ * both outputs NULL or not 16-byte aligned, height / width outside [1, 256]; CA_EUNSUPPORTED: the map's bitmap
+ * (rows x ceil(cols / 32) words) does not fit the LDS.  The _maps form shows every env its OWN map env_map[e]
+ * (an index outside the set: empty static part, agents still drawn, bit 2 of the fault word). */
+int cagpu_occupancy_grid(const CaParams *p, const CaState *s, const CaMap *map, const CaOccGrid *grid, void *stream);
+int cagpu_occupancy_grid_maps(const CaParams *p, const CaState *s, const CaMapSet *set, const CaOccGrid *grid, void *stream);
 
 /* Replaces: GA3CCADRLPolicy.find_next_action (policies/GA3CCADRLPolicy.py:49-84) + NetworkVPCore.predict_p
  * (GA3C_CADRL/network.py:24-41, the TF1 graph of the checkpoint) for every agent whose policy is CA_POL_GA3C_CADRL and
@@ -429,8 +458,8 @@ uint64_t cagpu_workspace_bytes(const CaParams *p);
  * bit 1 = an operand of the GA3C-CADRL network kernel left the range of its two-plane fp16 split (|x| >= 65504: a normalised
  * input or an activation; csrc/cagpu_ga3c.inc), i.e. some cagpu_ga3c call since the last clear chose its actions from
  * saturated values.
- * bit 2 = a map-set env's map index (CaMapSet.env_map) lay outside [0, num_maps) (cagpu_step_maps / cagpu_laserscan_maps,
- * v12): that env saw an empty map in some call since the last clear.
+ * bit 2 = a map-set env's map index (CaMapSet.env_map) lay outside [0, num_maps) (cagpu_step_maps / cagpu_laserscan_maps /
+ * cagpu_occupancy_grid_maps, v12): that env saw an empty map in some call since the last clear.
  * *faults receives the word; clear != 0 resets it.  0 in normal operation; check it wherever the host synchronises anyway. */
 int cagpu_device_faults(uint32_t *faults, int32_t clear);
 
