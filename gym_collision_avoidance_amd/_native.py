@@ -73,6 +73,10 @@ class CaOccGrid(C.Structure):
                 ("y_width", C.c_double)]
 
 
+class CaTraj(C.Structure):
+    _fields_ = [("rows", _P), ("episode", _P)]
+
+
 NET_FIELDS = ("lstm_kernel", "lstm_bias", "layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias", "fc1_kernel",
               "fc1_bias", "logits_kernel", "logits_bias", "input_mean", "input_std")
 
@@ -85,7 +89,8 @@ class CaNet(C.Structure):
 EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_reset", "cagpu_step", "cagpu_step_map", "cagpu_rollout",
            "cagpu_orca", "cagpu_observe", "cagpu_laserscan", "cagpu_ga3c", "cagpu_generate_cases", "cagpu_generate_cases_ragged", "cagpu_plan", "cagpu_debug_libm", "cagpu_device_faults", "cagpu_workspace_bytes",
            "cagpu_ga3c_packed_bytes", "cagpu_ga3c_pack", "cagpu_rollout_ring", "cagpu_ring_snapshots", "cagpu_debug_copy8", "cagpu_device_faults_async",
-           "cagpu_step_maps", "cagpu_laserscan_maps", "cagpu_occupancy_grid", "cagpu_occupancy_grid_maps")
+           "cagpu_step_maps", "cagpu_laserscan_maps", "cagpu_occupancy_grid", "cagpu_occupancy_grid_maps",
+           "cagpu_step_traj", "cagpu_rollout_traj")
 
 _lib = None
 
@@ -122,6 +127,8 @@ def lib():
     L.cagpu_laserscan_maps.argtypes = [PP, PS, C.POINTER(CaMapSet), C.POINTER(CaScan), _P]
     L.cagpu_occupancy_grid.argtypes = [PP, PS, C.POINTER(CaMap), C.POINTER(CaOccGrid), _P]
     L.cagpu_occupancy_grid_maps.argtypes = [PP, PS, C.POINTER(CaMapSet), C.POINTER(CaOccGrid), _P]
+    L.cagpu_step_traj.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaMap), C.POINTER(CaMapSet), C.POINTER(CaTraj), _P]
+    L.cagpu_rollout_traj.argtypes = [PP, PS, PO, _P, PA, C.c_int32, C.c_int32, C.c_int64, C.POINTER(CaTraj), _P]
     L.cagpu_observe.argtypes = [PP, PS, PO, _P]
     L.cagpu_plan.argtypes = [PP, PS, _P]
     L.cagpu_orca.argtypes = [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int32,

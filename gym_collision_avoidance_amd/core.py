@@ -145,6 +145,9 @@ class BatchedSim(object):
         # (the first probe -- it creates the side stream and the pinned word: milliseconds -- on the second launch of a
         # simulator's life, not 256 launches in, in the middle of somebody's timed loop)
         self._steps_since_probe = 254
+        # the trajectory tape (record_trajectories): None = never switched on
+        self._traj, self._traj_on = None, False
+        self._ct = nat.CaTraj()   # the slot a single-step launch records into (rewritten before every such launch)
 
     # ---------------------------------------------------------------- what the outside reads
     # `state` and the four outputs are those of the step last handed out: reading them goes through sync(), which rewinds a
@@ -468,6 +471,10 @@ class BatchedSim(object):
                                        None if h is None else h.data_ptr(), None if m is None else m.data_ptr(),
                                        self._stream()))
         self._keep = [c, h, m]  # keep alive until the stream has consumed them
+        if self._traj is not None:   # a host-side reset logs no row but ends the episode of the envs it touches (tape "epoch")
+            tr = self._traj
+            tr["epoch"] = tr["epoch"] + (1 if m is None else (m != 0).to(torch.int32))
+            tr["open"] = None
         if self._maps is not None and self._map_rng is not None:
             # a fresh key per explicit reset: the auto-reset draws of the new episodes are not those of the last ones
             self._maps.map_seed = int(self._map_rng.integers(1, 1 << 64, dtype=np.uint64))
@@ -620,6 +627,8 @@ class BatchedSim(object):
         (CaState.ext_state); None: nobody."""
         if self._la is not None:
             self.sync()
+        if self._traj_on:     # (first: a tape that is full raises before anything of this step has happened)
+            self._traj_slot()
         if self._rvo is not None:
             self._rvo_draw()
         if ext_state is not None or self._cs.ext_state:
@@ -633,7 +642,11 @@ class BatchedSim(object):
             fa = self._fast_args
             if fa is None:
                 ar = None if self._ar is None else C.byref(self._ar)
-                if self._maps is not None:
+                if self._traj_on:
+                    fa = (self.lib.cagpu_step_traj, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
+                                                     C.byref(self._map) if (self._map is not None and self._maps is None) else None,
+                                                     None if self._maps is None else C.byref(self._maps), C.byref(self._ct)))
+                elif self._maps is not None:
                     fa = (self.lib.cagpu_step_maps, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
                                                      C.byref(self._maps)))
                 elif self._map is not None:
@@ -665,7 +678,14 @@ class BatchedSim(object):
             e = self.ga3c(None if e is None else self._ga3c_ext)
         if self.fresh_outputs:
             self._new_outputs()
-        if self._maps is not None:
+        if self._traj_on:
+            nat.check(self.lib.cagpu_step_traj(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
+                                               None if e is None else e.data_ptr(),
+                                               None if self._ar is None else C.byref(self._ar),
+                                               C.byref(self._map) if (self._map is not None and self._maps is None) else None,
+                                               None if self._maps is None else C.byref(self._maps), C.byref(self._ct),
+                                               self._stream()))
+        elif self._maps is not None:
             nat.check(self.lib.cagpu_step_maps(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
                                                None if e is None else e.data_ptr(),
                                                None if self._ar is None else C.byref(self._ar), C.byref(self._maps),
@@ -694,10 +714,18 @@ class BatchedSim(object):
         e = self._dev(ext_actions, torch.float64)
         if self.fresh_outputs:
             self._new_outputs()
-        nat.check(self.lib.cagpu_rollout(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                         None if e is None else e.data_ptr(),
-                                         None if self._ar is None else C.byref(self._ar), int(n_steps),
-                                         self._stream()))
+        if self._traj_on:
+            chunk, ct = self._traj_chunk(int(n_steps))
+            nat.check(self.lib.cagpu_rollout_traj(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
+                                                  None if e is None else e.data_ptr(),
+                                                  None if self._ar is None else C.byref(self._ar), int(n_steps), 0, 0,
+                                                  C.byref(ct), self._stream()))
+            self._traj_commit(chunk)
+        else:
+            nat.check(self.lib.cagpu_rollout(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
+                                             None if e is None else e.data_ptr(),
+                                             None if self._ar is None else C.byref(self._ar), int(n_steps),
+                                             self._stream()))
         self._keep = [e]
         self._apply_sensor_variants()
         return self._obs, self._rewards, self._game_over
@@ -764,11 +792,16 @@ class BatchedSim(object):
                                  "draws, sensor variants or a static map) -- use step()")
         if self._cs.ext_state:   # (CaState.ext_state belongs to the ONE step() call that was given it: see rollout())
             self._cs.ext_state, self._ext_state = None, None
+        rec = self._traj_on      # (one look per fill: with recording off a fill does what it did before the tape existed)
+        if rec:
+            fit = self._traj_fit()   # (a full tape raises here, before anything changes)
         if la["adaptive"] and la["slots"] is not None and la["t"] >= la["len"]:   # the last ring was used up: a longer one --
             la["streak"] += 1                                                     # after a rewind, only the second in a row
             if la["streak"] >= 2:
                 la["cur"] = min(la["n"], 2 * la["cur"])
         k = la["cur"]
+        if rec and fit < k:
+            k = fit                  # (a ring is shortened to what the tape's budget still holds)
         # Everything a launch needs that does not depend on the moment of the call -- the ring's tensors, the CaOut that names
         # them, the rewind mode, the slot views handed out later -- was prepared behind the PREVIOUS launch (_la_prepare): a
         # caller who synchronises around K steps (bench.py's timed block) has the device idle until this launch is submitted
@@ -779,10 +812,18 @@ class BatchedSim(object):
         la["ring"] = prep["ring"]
         if not prep["in_kernel"]:
             la["snap"].copy_(self._slab)
-        rc = self.lib.cagpu_rollout_ring(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, prep["delta"],
-                                         _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
-        if rc != 0:
-            nat.check(rc)
+        if rec:               # the ring's own chunk of the tape: slot t of the launch records step t
+            chunk, ct = self._traj_chunk(k, prep.get("traj"))
+            rc = self.lib.cagpu_rollout_traj(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, 1, prep["delta"], C.byref(ct),
+                                             _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
+            if rc != 0:
+                nat.check(rc)
+            la["traj"] = self._traj_commit(chunk)
+        else:
+            rc = self.lib.cagpu_rollout_ring(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, prep["delta"],
+                                             _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
+            if rc != 0:
+                nat.check(rc)
         la["slots"] = prep["slots"]
         la["co_live"] = prep["co"]      # (keeps the ctypes struct the launch was given alive)
         la["t"], la["len"] = 0, k
@@ -823,6 +864,7 @@ class BatchedSim(object):
         # (the kernels write 0 / 1 bytes: reinterpreted as bool without a conversion kernel)
         slots = list(zip(obs.unbind(0), rew.unbind(0), done.view(torch.bool).unbind(0), over.view(torch.bool).unbind(0)))
         return dict(k=k, key=key, ring=ring, co=co, co_ref=C.byref(co), ar_ref=ar_ref, in_kernel=in_kernel, slots=slots,
+                    traj=self._traj_alloc(k) if self._traj_on else None,   # (always its own tensors, fresh ring or not)
                     delta=(la["snap"].data_ptr() - self._slab.data_ptr()) if in_kernel else 0)
 
     def step_lookahead(self):
@@ -853,6 +895,10 @@ class BatchedSim(object):
                 la["streak"] = 0
         if not la["fresh"]:
             la["ring"] = None      # (the current outputs below live in it: the next fill must not overwrite them)
+        ch = la.pop("traj", None)
+        if ch is not None and t < k:   # the tape keeps the t slots handed out; the replay below records nothing
+            self._traj["bytes"] -= (k - t) * self.traj_step_bytes
+            ch["n"] = t
         if t > 0:                  # the outputs of the last step handed out are the simulator's current outputs
             own = (lambda x: x.clone()) if la["fresh"] else (lambda x: x)   # (a fresh ring's slots belong to the caller)
             self._obs, self._rewards, self._done, self._game_over = own(obs[t - 1]), own(rew[t - 1]), own(done[t - 1]), own(over[t - 1])
@@ -864,6 +910,124 @@ class BatchedSim(object):
             if t > 0:              # (rewrites slot t - 1 with the values it already holds)
                 nat.check(self.lib.cagpu_rollout(C.byref(self.p), C.byref(self._cs), C.byref(self._co), None,
                                                  None if self._ar is None else C.byref(self._ar), t, self._stream()))
+
+    # ---------------------------------------------------------------- the trajectory tape (include/cagpu.h CaTraj)
+    TRAJ_BLOCK_BYTES = 8 << 20   # step(): slots are taken from blocks of about this size (at most 64 slots), not a tensor per step
+
+    @property
+    def traj_step_bytes(self):
+        """bytes of one recorded step: 96 per agent slot + 4 per env"""
+        return 96 * self.E * self.N + 4 * self.E
+
+    def record_trajectories(self, max_bytes=1 << 30):
+        """Record every agent's trajectory on the device from the next step on: the step kernels themselves write the
+        reference's Agent.global_state_history row (agent.py:257-289) of every agent that moves, through step(),
+        rollout() and step_lookahead() alike (cagpu_step_traj / cagpu_rollout_traj).  Off by default -- the reference's
+        Config.STORE_HISTORY default does not switch it on for a batch (96 bytes per agent and step).  max_bytes: the
+        budget of the tape; the launch that would take it past the budget raises CagpuError BEFORE it runs (nothing is
+        dropped silently, the tape stays valid; clear_trajectories() makes room); a look-ahead ring is shortened to what
+        still fits.  Calling it again changes the budget and keeps the tape."""
+        self.sync()
+        if self._traj is None:
+            self._traj = dict(chunks=[], bytes=0, block=None, open=None,
+                              epoch=torch.zeros((self.E,), dtype=torch.int32, device=self.device))
+        self._traj["max_bytes"] = int(max_bytes)
+        self._traj_switch(True)
+
+    def stop_recording(self):
+        """the steps from here on are not recorded; the tape stays readable (trajectories()) until clear_trajectories()"""
+        self.sync()
+        self._traj_switch(False)
+
+    def clear_trajectories(self):
+        """forget the tape recorded so far (T = 0); recording stays as it is (on / off, budget)"""
+        self.sync()
+        tr = self._traj
+        if tr is not None:
+            tr["chunks"], tr["bytes"], tr["block"], tr["open"] = [], 0, None, None
+
+    def _traj_switch(self, on):
+        self._traj_on = bool(on)
+        self._fast_args = None
+        if self._traj is not None:
+            self._traj["open"] = None
+        if self._la is not None:
+            self._la["prep"] = None   # (a prepared ring launch carries, or lacks, its chunk of the tape)
+
+    def _traj_fit(self):
+        """how many more steps the budget holds; raises when it holds none"""
+        tr, per = self._traj, self.traj_step_bytes
+        fit = (tr["max_bytes"] - tr["bytes"]) // per
+        if fit < 1:
+            raise nat.CagpuError("trajectory tape full: %d of max_bytes = %d bytes recorded, one more step takes %d bytes "
+                                 "(96 * E * N + 4 * E) -- read trajectories() and call clear_trajectories(), or "
+                                 "record_trajectories(max_bytes=...) with a larger budget; no step was taken"
+                                 % (tr["bytes"], tr["max_bytes"], per))
+        return fit
+
+    def _traj_alloc(self, n):
+        return (torch.empty((n, self.E, self.N, 12), dtype=torch.float64, device=self.device),
+                torch.empty((n, self.E), dtype=torch.int32, device=self.device))
+
+    def _traj_slot(self):
+        """point self._ct at the next slot of the current block (step(): one slot per launch)"""
+        tr, per = self._traj, self.traj_step_bytes
+        fit = self._traj_fit()
+        b = tr["block"]
+        if b is None or b["used"] >= b["cap"]:
+            cap = int(max(1, min(64, self.TRAJ_BLOCK_BYTES // per, fit)))
+            rows, ep = self._traj_alloc(cap)
+            b = tr["block"] = dict(rows=rows, ep=ep, used=0, cap=cap)
+            tr["open"] = None
+        c = tr["open"]
+        if c is None:       # a run of consecutive slots of one block under one epoch
+            c = tr["open"] = dict(rows=b["rows"], ep=b["ep"], start=b["used"], n=0, epoch=tr["epoch"])
+            tr["chunks"].append(c)
+        self._ct.rows = b["rows"].data_ptr() + b["used"] * self.E * self.N * 96
+        self._ct.episode = b["ep"].data_ptr() + b["used"] * self.E * 4
+        b["used"] += 1
+        c["n"] += 1
+        tr["bytes"] += per
+
+    def _traj_chunk(self, n, tensors=None):
+        """a chunk of n slots for ONE multi-step launch -> (chunk, CaTraj); raises when the budget does not hold n steps"""
+        tr, per = self._traj, self.traj_step_bytes
+        if self._traj_fit() < n:
+            raise nat.CagpuError("trajectory tape: %d steps of %d bytes (96 * E * N + 4 * E) do not fit the %d bytes left of "
+                                 "max_bytes = %d -- clear_trajectories() or a larger budget; no step was taken"
+                                 % (n, per, tr["max_bytes"] - tr["bytes"], tr["max_bytes"]))
+        if tensors is None or tensors[0].shape[0] != n:
+            tensors = self._traj_alloc(n)
+        chunk = dict(rows=tensors[0], ep=tensors[1], start=0, n=n, epoch=tr["epoch"])
+        return chunk, nat.CaTraj(rows=tensors[0].data_ptr(), episode=tensors[1].data_ptr())
+
+    def _traj_commit(self, chunk):
+        tr = self._traj
+        tr["chunks"].append(chunk)
+        tr["bytes"] += chunk["n"] * self.traj_step_bytes
+        tr["open"] = None
+        return chunk
+
+    def trajectories(self):
+        """The tape recorded since record_trajectories() / the last clear_trajectories(), in step order, on the device:
+          rows     float64 [T, E, N, 12]: columns 0 - 10 the reference's global_state_history row (t, px, py, gx, gy,
+                   radius, pref_speed, vx, vy, speed, heading), column 11 the row's index in the agent's history --
+                   or -1 for an agent that did not move in that step, whose other columns are UNSPECIFIED;
+          episode  int32 [T, E]: the env's auto-reset count as the step started;
+          epoch    int32 [T, E]: the host-side resets (reset() / reset_from_table()) of the env since recording began --
+                   a reset logs no row but ends the episode (trajectory.episodes splits where either counter changes).
+        T = the steps handed out (goes through sync()).  Returns copies."""
+        self.sync()
+        tr = self._traj
+        E, N, dev = self.E, self.N, self.device
+        cs = [] if tr is None else [c for c in tr["chunks"] if c["n"] > 0]
+        if not cs:
+            return {"rows": torch.empty((0, E, N, 12), dtype=torch.float64, device=dev),
+                    "episode": torch.empty((0, E), dtype=torch.int32, device=dev),
+                    "epoch": torch.empty((0, E), dtype=torch.int32, device=dev)}
+        sl = lambda c, t: t[c["start"]:c["start"] + c["n"]]
+        return {"rows": torch.cat([sl(c, c["rows"]) for c in cs]), "episode": torch.cat([sl(c, c["ep"]) for c in cs]),
+                "epoch": torch.cat([c["epoch"].unsqueeze(0).expand(c["n"], E) for c in cs])}
 
     # ---------------------------------------------------------------- statistics
     def _fault_probe(self):

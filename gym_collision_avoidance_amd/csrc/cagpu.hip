@@ -84,7 +84,38 @@ struct KArgs {
   int64_t map_words;         // rows * words per row: one map of the set
   int32_t num_maps;
   unsigned long long map_seed;  // != 0: an auto-reset draws the env's next map (CaMapSet.map_seed)
+  // trajectory tape (cagpu_step_traj / cagpu_rollout_traj; nullptr everywhere else): slot 0 of CaTraj.rows [n, E, N, 12] and
+  // of CaTraj.episode [n, E].  Step t of a launch writes slot t whether or not the outputs form a ring: the slot strides
+  // are E N 12 doubles / E ints (the kernels derive them from p).
+  double* traj_rows;
+  int32_t* traj_ep;
 };
+
+// One row of the trajectory tape (CaTraj): the reference's global_state_history row (agent.py:275-287) + its index.
+// 96 bytes = six 16-byte stores; the rows of a tile's lanes are contiguous.
+__device__ __forceinline__ void traj_store(double* row, const double t, const double px, const double py, const double gx,
+                                           const double gy, const double rad, const double ps, const double vx,
+                                           const double vy, const float speed, const double heading, const int index) {
+  double2* q = reinterpret_cast<double2*>(row);
+  q[0] = make_double2(t, px);
+  q[1] = make_double2(py, gx);
+  q[2] = make_double2(gy, rad);
+  q[3] = make_double2(ps, vx);
+  q[4] = make_double2(vy, static_cast<double>(speed));
+  q[5] = make_double2(heading, static_cast<double>(index));
+}
+// ... columns 1 - 11 of a row whose column 0 (the clock before the move) is already out
+__device__ __forceinline__ void traj_store_tail(double* row, const double px, const double py, const double gx, const double gy,
+                                                const double rad, const double ps, const double vx, const double vy,
+                                                const float speed, const double heading, const int index) {
+  row[1] = px;
+  double2* q = reinterpret_cast<double2*>(row);
+  q[1] = make_double2(py, gx);
+  q[2] = make_double2(gy, rad);
+  q[3] = make_double2(ps, vx);
+  q[4] = make_double2(vy, static_cast<double>(speed));
+  q[5] = make_double2(heading, static_cast<double>(index));
+}
 
 // A map-set env's grid (KArgs / ScanArgs .env_map): map m of the set, or nullptr -- no walls, no map memory read -- for an
 // index outside [0, num_maps), which raises bit 2 of the fault word when `report` (one lane per env reports).
@@ -688,6 +719,7 @@ __global__ __launch_bounds__(NT, MULTI ? (NC == 20 ? 2 : 4) : 1) void ca_kernel(
   const long tile_base = env0 * N;
   float* obs_tile = k.o.obs + tile_base * (6 + 7 * p.max_obs);  // the tile's observation rows (uniform: scalar arithmetic)
   long ring_a = 0, ring_e = 0;  // n-step kernel: this step's slot of the caller's output ring (cagpu_rollout_ring), in elements
+  long traj_a = 0, traj_e = 0;  // ... and of the trajectory tape (CaTraj), which advances in a plain rollout too
   long tile_cnt = static_cast<long>(p.num_envs) * N - tile_base;
   if (tile_cnt > tile_n) tile_cnt = tile_n;
 
@@ -1141,6 +1173,10 @@ LP1_UNROLL
         if (active && k.o.actions) reinterpret_cast<float2*>(k.o.actions)[i + ring_a] = make_float2(a0f, a1f);
         if (active && k.o.orca_vel)  // parity hook: the velocity rvo2 chose for this agent (RVOPolicy.py:93), 0 if not queried
           reinterpret_cast<float2*>(k.o.orca_vel)[i + ring_a] = rvo ? make_float2(v_orca.x, v_orca.y) : make_float2(0.f, 0.f);
+        // trajectory tape (CaTraj): who moves is known before the move, and the row's clock is the one BEFORE its increment:
+        // stored here, so that nothing but one predicate lives across the move for the rest of the row
+        const bool moved = active && !(r.flags & (CA_AT_GOAL | CA_OUT_OF_TIME | CA_IN_COLLISION));
+        if (k.traj_rows && moved) k.traj_rows[(i + traj_a) * 12] = r.t;
         if (active) {
           if (r.flags & (CA_AT_GOAL | CA_OUT_OF_TIME | CA_IN_COLLISION)) {
             if (r.flags & CA_AT_GOAL) r.flags |= CA_WAS_AT_GOAL;
@@ -1183,6 +1219,12 @@ LP1_UNROLL
             r.step_num += 1;
             if (r.tr <= 0.0) r.flags |= CA_OUT_OF_TIME;
           }
+        }
+        if (k.traj_rows && active) {  // trajectory tape (CaTraj): after the move, before any auto-reset of this step
+          double* row = k.traj_rows + (i + traj_a) * 12;
+          if (moved) traj_store_tail(row, r.px, r.py, r.gx, r.gy, r.rad, r.ps, r.vx, r.vy, r.act0, r.heading, r.step_num - 1);
+          else row[11] = -1.0;
+          if (a == 0 && k.traj_ep) k.traj_ep[e + traj_e] = reset_cnt;
         }
       }
       do_sense = active;
@@ -1600,6 +1642,8 @@ LP1_UNROLL
       obs_tile += k.ring_obs;  // (0 unless the caller keeps every step's outputs: cagpu_rollout_ring)
       ring_a += k.ring_agent;
       ring_e += k.ring_env;
+      traj_a += static_cast<long>(p.num_envs) * N;
+      traj_e += p.num_envs;
     }
   } else {
     one_step();
@@ -1779,6 +1823,8 @@ void ring_advance(KArgs& k) {
   k.o.game_over += k.ring_env;
   if (k.o.actions) k.o.actions += 2 * k.ring_agent;
   if (k.o.orca_vel) k.o.orca_vel += 2 * k.ring_agent;
+  if (k.traj_rows) k.traj_rows += static_cast<int64_t>(k.p.num_envs) * k.p.num_agents * 12;  // (a tape advances in a plain rollout too)
+  if (k.traj_ep) k.traj_ep += k.p.num_envs;
 }
 
 template <int NT, bool STAGE, int NC, bool MULTI, bool RO, int TE = 0>
@@ -1941,9 +1987,14 @@ int launch_pipe2(const KArgs& k0, hipStream_t st) {
     const long per_cu = (160 * 1024) / static_cast<long>(G::LDS) < 4 ? (160 * 1024) / static_cast<long>(G::LDS) : 4;
     if (grid > cus && grid <= per_cu * cus) k.yield_t = CAGPU_PIPE_YIELD_T;
   }
-  std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_pipe_kernel<%d, %d, %s> grid=%u lds=%zu mode=%d%s", NC, TE,
-                MULTI ? "true" : "false", grid, static_cast<size_t>(G::LDS), k.mode, k.yield_t > 0 ? " fair" : "");
-  if (MULTI && k.yield_t > 0) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, MULTI>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+  std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_pipe_kernel<%d, %d, %s> grid=%u lds=%zu mode=%d%s%s", NC, TE,
+                MULTI ? "true" : "false", grid, static_cast<size_t>(G::LDS), k.mode, k.yield_t > 0 ? " fair" : "",
+                k.traj_rows ? " traj" : "");
+  // (recording is a template flag: the instantiations without it are the code they were before the tape existed)
+  if (k.traj_rows) {
+    if (MULTI && k.yield_t > 0) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, MULTI, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+    else hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, false, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+  } else if (MULTI && k.yield_t > 0) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, MULTI>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
   else hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, false>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
@@ -2137,7 +2188,13 @@ static int check_map_set(const CaMapSet* set, const char* who) {
 
 static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const double* ext, const CaAutoReset* ar,
                      int32_t n_steps, void* stream, const CaMap* map = nullptr, const bool ring = false,
-                     const int64_t snapshot_delta = 0, const bool query_snapshot = false, const CaMapSet* set = nullptr) {
+                     const int64_t snapshot_delta = 0, const bool query_snapshot = false, const CaMapSet* set = nullptr,
+                     const CaTraj* traj = nullptr, const bool want_traj = false) {
+  if (want_traj) {  // (first: a bad tape is reported as such whatever else is wrong with the call)
+    if (!traj || !traj->rows) return fail(CA_EINVAL, "cagpu: NULL CaTraj or CaTraj.rows%s");
+    if ((reinterpret_cast<uintptr_t>(traj->rows) & 15u) || (reinterpret_cast<uintptr_t>(traj->episode) & 3u))
+      return fail(CA_EINVAL, "cagpu: CaTraj.rows must be 16-byte aligned (CaTraj.episode: 4-byte)%s");
+  }
   int rc = check_params(p, s, o);
   if (rc) return rc;
   if (set && (rc = check_map_set(set, "cagpu_step_maps"))) return rc;
@@ -2167,6 +2224,7 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
     k.map_seed = ar ? set->map_seed : 0;  // (draws happen at auto-resets only)
   }
   k.n_steps = n_steps; k.mode = MODE_STEP;
+  if (want_traj) { k.traj_rows = traj->rows; k.traj_ep = traj->episode; }
   k.inv_rvo_dt = 1.0 / p->rvo_dt;
   {
     static std::atomic<int> seq{0};
@@ -2208,6 +2266,18 @@ int cagpu_step_maps(const CaParams* p, const CaState* s, const CaOut* o, const d
                     const CaMapSet* set, void* stream) {
   if (!set) return fail(CA_EINVAL, "cagpu_step_maps: NULL CaMapSet%s");
   return step_impl(p, s, o, ext_actions, ar, 1, stream, nullptr, false, 0, false, set);
+}
+
+int cagpu_step_traj(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
+                    const CaMap* map, const CaMapSet* set, const CaTraj* traj, void* stream) {
+  if (map && set) return fail(CA_EINVAL, "cagpu_step_traj: a CaMap and a CaMapSet at once%s");
+  return step_impl(p, s, o, ext_actions, ar, 1, stream, map, false, 0, false, set, traj, true);
+}
+
+int cagpu_rollout_traj(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
+                       int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj* traj, void* stream) {
+  if (!ring && snapshot_delta != 0) return fail(CA_EINVAL, "cagpu_rollout_traj: snapshot_delta without ring%s");
+  return step_impl(p, s, o, ext_actions, ar, n_steps, stream, nullptr, ring != 0, snapshot_delta, false, nullptr, traj, true);
 }
 
 static int laserscan_impl(const CaParams* p, const CaState* s, const CaMap* map, const CaScan* scan, void* stream,

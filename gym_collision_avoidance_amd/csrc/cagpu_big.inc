@@ -152,12 +152,16 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
       if (active && k.o.orca_vel)
         reinterpret_cast<float2*>(k.o.orca_vel)[i] = rvo ? make_float2(v_orca.x, v_orca.y) : make_float2(0.f, 0.f);
       // ================= move (Agent.take_action, agent.py:192-241)
+      const double t_pre = r.t;         // (the trajectory row holds the clock and the index BEFORE their increments)
+      const int index_pre = r.step_num;
+      bool moved = false;
       if (active) {
         if (r.flags & (CA_AT_GOAL | CA_OUT_OF_TIME | CA_IN_COLLISION)) {
           if (r.flags & CA_AT_GOAL) r.flags |= CA_WAS_AT_GOAL;
           if (r.flags & CA_IN_COLLISION) r.flags |= CA_WAS_IN_COLLISION;
           r.vx = r.vy = 0.0;
         } else {
+          moved = true;
           r.act0 = a0f;
           r.act1 = a1f;
           const double a0 = a0f, a1 = a1f;
@@ -194,6 +198,12 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
           r.step_num += 1;
           if (r.tr <= 0.0) r.flags |= CA_OUT_OF_TIME;
         }
+      }
+      if (k.traj_rows && active) {  // trajectory tape (CaTraj): after the move, before any auto-reset of this step
+        double* row = k.traj_rows + i * 12;   // (one launch per step: the host advances the slot)
+        if (moved) traj_store(row, t_pre, r.px, r.py, r.gx, r.gy, r.rad, r.ps, r.vx, r.vy, r.act0, r.heading, index_pre);
+        else row[11] = -1.0;
+        if (a == 0 && k.traj_ep) k.traj_ep[e] = reset_cnt;
       }
     }
 

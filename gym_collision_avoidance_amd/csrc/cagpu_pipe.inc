@@ -230,7 +230,10 @@ struct Geo {
 #define PIPE_ROLE_KARGS() const KArgs& k = karg; const CaParams& p = k.p
 #endif
 
-template <int NC, int TE, bool MULTI, bool FAIR = false>
+// TRAJ: the instantiation also records the trajectory tape (CaTraj, KArgs.traj_rows != nullptr).  A template flag and not
+// a uniform test: the programmes below are tuned down to their register counts, and the instantiations without the flag are
+// the code they were before the tape existed.
+template <int NC, int TE, bool MULTI, bool FAIR = false, bool TRAJ = false>
 __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
   static_assert(MULTI || !FAIR, "progress-fair priorities belong to the n-step kernel");
   using G = Geo<NC, TE>;
@@ -432,6 +435,9 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
     }
 #endif
     long out_base = tile_base, out_env = env0;  // n-step kernel: + this step's slot of the caller's output ring (cagpu_rollout_ring)
+    // trajectory tape (TRAJ): this tile's rows / its envs' episode entries in the slot of the current step (uniform pointers)
+    double* traj_tile = TRAJ ? k.traj_rows + tile_base * 12 : nullptr;
+    int32_t* traj_ep = (TRAJ && k.traj_ep) ? k.traj_ep + env0 : nullptr;
     PT(0);
     double px = 0.0, py = 0.0, vx = 0.0, vy = 0.0, heading = 0.0;
     float act0 = 0.f, act1 = 0.f;
@@ -730,6 +736,17 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         sh_t[lane] = l_t; sh_slt[lane] = l_slt; sh_epr[lane] = l_epr; sh_td[lane] = l_td;
       }
       ep_step += 1;
+      if (TRAJ) {
+        // The trajectory row (CaTraj), here because the agent wave waits for P3 below anyway: the clock and the index are
+        // still those BEFORE their increments, position / velocity / heading those after the move, the parked goal is the
+        // one the move used (StaticPolicy: the position), and no auto-reset of this step has happened yet (A4).
+        if (active) {
+          double* row = traj_tile + __mul24(lane, 12);
+          if (moved) traj_store(row, sh_t[lane], px, py, sh_gx[lane], sh_gy[lane], sh_rad[lane], sh_ps[lane], vx, vy, mv_a0, heading, step_num);
+          else row[11] = -1.0;
+          if (a == 0 && traj_ep) traj_ep[le] = reset_cnt;
+        }
+      }
       if (moved) {
         act0 = mv_a0; act1 = mv_a1;
         step_num += 1;
@@ -892,6 +909,10 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         obs_tile += k.ring_obs;
         out_base += k.ring_agent;
         out_env += k.ring_env;
+        if (TRAJ) {  // (the tape's slots advance whether or not the outputs form a ring)
+          traj_tile += static_cast<long>(p.num_envs) * N * 12;
+          if (traj_ep) traj_ep += p.num_envs;
+        }
       }
       __syncthreads();  // B_5: the plan of the next step (n-step kernel only; a FULL barrier: this step's stores are out)
       if (FAIR) {

@@ -213,8 +213,13 @@ class Agent(object):
 
     @property
     def global_state_history(self):
-        """[step, 11] trajectory log (agent.py:257-289), recorded by the env when Config.STORE_HISTORY (host side,
-        single-env mode)."""
+        """[step, 11] trajectory log (agent.py:257-289): with env.record_trajectories() the current episode's rows of the
+        device tape (written by the step kernels; batched envs, and a single env without Config.STORE_HISTORY), otherwise
+        what the env recorded on the host under Config.STORE_HISTORY (single-env mode)."""
+        if self._env is not None:
+            h = self._env._tape_history(self._e, self._a)
+            if h is not None:
+                return h
         return np.array(self._history).reshape(-1, self.global_state_dim)
 
     def set_state(self, px, py, vx=None, vy=None, heading=None):

@@ -137,6 +137,7 @@ class CollisionAvoidanceEnv(Env):
         self._all_agents = None
         self._host_policies, self._host_by_env, self._groups = [], None, []
         self._host_dynamics, self._hostdyn_by_env, self._ext_state = [], None, None
+        self._traj_req = None     # record_trajectories(): dict(max_bytes) while recording is asked for
 
     # ------------------------------------------------------------------ configuration (reference setters)
     def set_agents(self, agents):
@@ -402,6 +403,8 @@ class CollisionAvoidanceEnv(Env):
             params = core.make_params(E, N, max_obs=K, ragged=int(ragged))
             self._sim = core.BatchedSim(params, device=self.device)
             self._sim_key = key
+        if self._traj_req is not None and not self._sim._traj_on:   # (asked for before reset(), or the batch was rebuilt)
+            self._sim.record_trajectories(**self._traj_req)
         sim, p = self._sim, self._sim.p
         p.obs_clip, p.sort_mode, p.game_over_mode = clip, sort, over
         p.rvo_max_neighbors = Config.MAX_NUM_AGENTS_IN_ENVIRONMENT
@@ -650,7 +653,7 @@ class CollisionAvoidanceEnv(Env):
         """host copy of the device state, refreshed at most once per step"""
         if self._snap is None:
             st = self._sim.state
-            snap = {n: st[n].cpu().numpy() for n in _F64 + ("flags", "step_num", "last_action")}
+            snap = {n: st[n].cpu().numpy() for n in _F64 + ("flags", "step_num", "last_action", "reset_count")}
             self._snap = snap
         return self._snap
 
@@ -777,6 +780,63 @@ class CollisionAvoidanceEnv(Env):
         """bool device tensor [E, N, H, W]: every agent's OccupancyGridSensor window of the current state (H x W =
         y_width x x_width in map cells); None unless some agent of the batch lists the sensor."""
         return None if self._sim is None else self._sim.occ
+
+    # ------------------------------------------------------------------ trajectories (core.BatchedSim.record_trajectories)
+    def record_trajectories(self, on=True, max_bytes=None):
+        """Record every agent's trajectory ON THE DEVICE, inside the step kernels (the batched form of the reference's
+        Config.STORE_HISTORY log, agent.py:257-289): off by default whatever Config.STORE_HISTORY says -- 96 bytes per
+        agent and step.  May be called before or after reset() and survives reset().  max_bytes: the tape's budget
+        (default 1 GiB); the step that would exceed it raises CagpuError and takes no step."""
+        if not on:
+            self._traj_req = None
+            if self._sim is not None:
+                self._sim.stop_recording()
+            return
+        self._traj_req = {} if max_bytes is None else {"max_bytes": int(max_bytes)}
+        if self._sim is not None:
+            self._sim.record_trajectories(**self._traj_req)
+
+    def trajectories(self):
+        """the tape as device tensors: {"rows": float64 [T, E, N, 12], "episode": int32 [T, E], "epoch": int32 [T, E]}
+        (core.BatchedSim.trajectories); T = the steps taken since recording started or was last cleared"""
+        if self._sim is None:
+            raise RuntimeError("call reset() before trajectories()")
+        return self._sim.trajectories()
+
+    def clear_trajectories(self):
+        if self._sim is not None:
+            self._sim.clear_trajectories()
+        self._snap = None
+
+    def episode_histories(self, env_index=0):
+        """The recorded episodes of one env (trajectory.episodes): a list over episodes of lists over agent slots of
+        [len, 11] arrays -- each the reference's `agent.global_state_history[:step_num]` of that episode.  Only that
+        env's part of the tape is copied to the host."""
+        from gym_collision_avoidance_amd import trajectory
+        e = int(env_index)
+        tp = self.trajectories()
+        return trajectory.episodes(tp["rows"][:, e:e + 1], tp["episode"][:, e:e + 1], 0, epoch=tp["epoch"][:, e:e + 1])
+
+    def _tape_history(self, e, a):
+        """the CURRENT episode's [step_num, 11] log of agent (e, a) from the device tape, or None where the tape is not
+        the log's source (recording off; a single env under Config.STORE_HISTORY keeps its host-side log)"""
+        sim = self._sim
+        if sim is None or not sim._traj_on or (Config.STORE_HISTORY and self.num_envs == 1):
+            return None
+        snap = self._snapshot()
+        cache = snap.setdefault("_hist", {})
+        if e not in cache:
+            tp = sim.trajectories()
+            cur = None
+            if tp["rows"].shape[0]:
+                # the tape's last episode of this env is the current one unless a reset (on the device or from the host)
+                # came after its last recorded step: then the current episode has no row yet
+                same = (int(tp["episode"][-1, e]) == int(snap["reset_count"][e]) and
+                        int(tp["epoch"][-1, e]) == int(sim._traj["epoch"][e]))
+                if same:
+                    cur = self.episode_histories(e)[-1]
+            cache[e] = cur if cur is not None else [np.zeros((0, 11)) for _ in range(sim.N)]
+        return cache[e][a]
 
     # ------------------------------------------------------------------ batched extras
     def rollout(self, n_steps):

@@ -247,6 +247,24 @@ typedef struct CaOccGrid {
   double x_width, y_width; /* metres: the window spans [px - x_width / 2, px + x_width / 2) x (py - y_width / 2, py + y_width / 2] */
 } CaOccGrid;
 
+/* Trajectory tape of cagpu_step_traj / cagpu_rollout_traj: the reference's Agent.global_state_history rows
+ * (agent.py:257-289, appended by Agent.take_action with Config.STORE_HISTORY), written by the step kernels themselves.
+ * Step t of a call (t = 0 .. n_steps - 1; a single step: t = 0) writes slot t.  Per (slot, env, agent slot):
+ *   - an agent that gets past the done gate of Agent.take_action in this step writes all 12 columns:
+ *       0 t BEFORE the increment, 1-2 position, 3-4 goal, 5 radius, 6 pref_speed, 7-8 velocity,
+ *       9 speed (the float32 action speed widened: Agent.speed_global_frame = past_actions[0][0]), 10 heading
+ *     -- position / velocity / heading AFTER the move, goal / radius / pref_speed as held at the move (a StaticPolicy
+ *     agent's goal is its position) --, and 11 = Agent.step_num BEFORE the increment as a double: the index of the row in
+ *     the reference's global_state_history;
+ *   - an agent that does not move (done, or an absent slot of a ragged batch) writes column 11 = -1.0 ONLY: columns
+ *     0 - 10 of such a row are LEFT ALONE (whatever the caller's buffer held).
+ * The terminal step of an episode is recorded before an auto-reset replaces the state; the first step of the next episode
+ * has index 0 and an `episode` entry one higher. */
+typedef struct CaTraj {
+  double  *rows;     /* device [n_steps, E, N, 12], 16-byte aligned */
+  int32_t *episode;  /* device [n_steps, E] or NULL: CaState.reset_count[e] as the step STARTS (before its auto-reset) */
+} CaTraj;
+
 /* GA3C-CADRL network weights (policies/GA3C_CADRL/checkpoints/<run>/network_*.data-00000-of-00001): device float
  * pointers in the checkpoint's own layout, kernels row-major [in, out].  LSTM gate order i, j, f, o. */
 typedef struct CaNet {
@@ -424,6 +442,20 @@ int cagpu_rollout_ring(const CaParams *p, const CaState *s, const CaOut *o, cons
 /* 1: cagpu_rollout_ring with these arguments runs the kernel that takes the snapshot itself (snapshot_delta != 0 accepted);
  * 0: it does not; < 0: the arguments are invalid (CA_E*).  Host-only, launches nothing. */
 int cagpu_ring_snapshots(const CaParams *p, const CaState *s, const CaOut *o, const CaAutoReset *ar, int32_t n_steps);
+
+/* The step / rollout calls that also RECORD every agent's trajectory row (CaTraj), in the same kernels and with the same
+ * kernel selection, grid and block as the calls they mirror -- state, outputs and statistics are bit-identical to those:
+ *   cagpu_step_traj     = cagpu_step (map == set == NULL) / cagpu_step_map (map) / cagpu_step_maps (set); at most one of
+ *                         `map`, `set` may be non-NULL; records slot 0.
+ *   cagpu_rollout_traj  = cagpu_rollout (ring == 0) / cagpu_rollout_ring (ring != 0, with its snapshot_delta); records
+ *                         n_steps slots.
+ * Every kernel family records (the general, the pipelined single- and n-step and the large-env kernel).  CA_EINVAL, nothing
+ * launched: traj or traj->rows NULL, rows not 16-byte aligned, episode not 4-byte aligned, both map and set given -- plus
+ * whatever the mirrored call rejects.  cagpu_last_kernel() shows " traj" behind the pipelined kernel's name. */
+int cagpu_step_traj(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
+                    const CaMap *map, const CaMapSet *set, const CaTraj *traj, void *stream);
+int cagpu_rollout_traj(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
+                       int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj *traj, void *stream);
 
 /* The policy query of the NEXT step ahead of time (collision_avoidance_env.py:305-323 for the built-in RVO policy):
  * fills s->next_action from the CURRENT state and sets CA_PLAN_VALID, without stepping.  cagpu_step / cagpu_rollout keep
