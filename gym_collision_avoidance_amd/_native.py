@@ -77,6 +77,10 @@ class CaTraj(C.Structure):
     _fields_ = [("rows", _P), ("episode", _P)]
 
 
+class CaFinal(C.Structure):
+    _fields_ = [("obs", _P), ("flags", _P)]
+
+
 NET_FIELDS = ("lstm_kernel", "lstm_bias", "layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias", "fc1_kernel",
               "fc1_bias", "logits_kernel", "logits_bias", "input_mean", "input_std")
 
@@ -90,7 +94,7 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_orca", "cagpu_observe", "cagpu_laserscan", "cagpu_ga3c", "cagpu_generate_cases", "cagpu_generate_cases_ragged", "cagpu_plan", "cagpu_debug_libm", "cagpu_device_faults", "cagpu_workspace_bytes",
            "cagpu_ga3c_packed_bytes", "cagpu_ga3c_pack", "cagpu_rollout_ring", "cagpu_ring_snapshots", "cagpu_debug_copy8", "cagpu_device_faults_async",
            "cagpu_step_maps", "cagpu_laserscan_maps", "cagpu_occupancy_grid", "cagpu_occupancy_grid_maps",
-           "cagpu_step_traj", "cagpu_rollout_traj")
+           "cagpu_step_traj", "cagpu_rollout_traj", "cagpu_step_final", "cagpu_rollout_final")
 
 _lib = None
 
@@ -129,6 +133,10 @@ def lib():
     L.cagpu_occupancy_grid_maps.argtypes = [PP, PS, C.POINTER(CaMapSet), C.POINTER(CaOccGrid), _P]
     L.cagpu_step_traj.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaMap), C.POINTER(CaMapSet), C.POINTER(CaTraj), _P]
     L.cagpu_rollout_traj.argtypes = [PP, PS, PO, _P, PA, C.c_int32, C.c_int32, C.c_int64, C.POINTER(CaTraj), _P]
+    L.cagpu_step_final.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaMap), C.POINTER(CaMapSet), C.POINTER(CaTraj),
+                                   C.POINTER(CaFinal), _P]
+    L.cagpu_rollout_final.argtypes = [PP, PS, PO, _P, PA, C.c_int32, C.c_int32, C.c_int64, C.POINTER(CaTraj),
+                                      C.POINTER(CaFinal), _P]
     L.cagpu_observe.argtypes = [PP, PS, PO, _P]
     L.cagpu_plan.argtypes = [PP, PS, _P]
     L.cagpu_orca.argtypes = [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int32,
@@ -171,6 +179,28 @@ def debug_libm(op, a, b=None):
     o0, o1 = np.empty_like(a), np.empty_like(a)
     check(lib().cagpu_debug_libm(op, a.size, a.ctypes.data, None if b is None else b.ctypes.data, o0.ctypes.data, o1.ctypes.data))
     return o0, o1
+
+
+# the bits of a flag word the step kernels decide (everything but the policy / dynamics ids, the learning bits set by
+# set_plugins and PLAN_VALID, which belongs to the pipelined policy query)
+KERNEL_FLAG_BITS = AT_GOAL | WAS_AT_GOAL | IN_COLLISION | WAS_IN_COLLISION | OUT_OF_TIME | DONE | ABSENT
+
+
+def decode_flags(flags):
+    """Agent flag words (include/cagpu.h: CaState.flags, CaFinal.flags) -> {name: bool array of the same shape}:
+    `at_goal`, `in_collision`, `ran_out_of_time` -- the reference's Agent.is_at_goal / in_collision / ran_out_of_time
+    (agent.py:108-112) --, `done` and `absent` (an empty slot of a ragged batch: it carries at_goal and done as well, mask
+    with ~absent where only agents count).  Pure host-side bit tests: numpy arrays, torch tensors (any device, int32 as
+    the simulator keeps them) and plain ints all work."""
+    if not hasattr(flags, "__and__") or isinstance(flags, (list, tuple)):
+        import numpy as np
+        flags = np.asarray(flags)
+    if hasattr(flags, "dtype") and not hasattr(flags, "device"):   # numpy: uint32 words and int32 bit patterns alike
+        import numpy as np
+        flags = np.asarray(flags).astype(np.int64)
+    bit = lambda m: (flags & m) != 0
+    return {"at_goal": bit(AT_GOAL), "in_collision": bit(IN_COLLISION), "ran_out_of_time": bit(OUT_OF_TIME),
+            "done": bit(DONE), "absent": bit(ABSENT)}
 
 
 def check(rc):

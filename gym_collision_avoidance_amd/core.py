@@ -148,6 +148,9 @@ class BatchedSim(object):
         # the trajectory tape (record_trajectories): None = never switched on
         self._traj, self._traj_on = None, False
         self._ct = nat.CaTraj()   # the slot a single-step launch records into (rewritten before every such launch)
+        # the final record (keep_final): the terminal observation / flag words of the envs an auto-reset overwrites
+        self._fin_on, self._fin_obs, self._fin_flags = False, None, None
+        self._cf = nat.CaFinal()
 
     # ---------------------------------------------------------------- what the outside reads
     # `state` and the four outputs are those of the step last handed out: reading them goes through sync(), which rewinds a
@@ -166,6 +169,9 @@ class BatchedSim(object):
             setattr(self, name, value)
         return property(get, put)
     obs, rewards, done, game_over = _synced("_obs"), _synced("_rewards"), _synced("_done"), _synced("_game_over")
+    # the final record of the step last handed out (keep_final; None while it is off): float32 [E, N, W] / int32 [E, N]
+    # (uint32 bit patterns, nat.decode_flags), rows valid where `game_over` is set
+    final_obs, final_flags = _synced("_fin_obs"), _synced("_fin_flags")
     del _synced
 
     # ---------------------------------------------------------------- plumbing
@@ -260,6 +266,10 @@ class BatchedSim(object):
         mask a bool array broadcastable to [E, N]; after every step / reset / observe the rows of the masked agents are
         replaced by their rows under that pair.  None / []: switched off."""
         self.sync()
+        if variants and self._fin_on:
+            raise nat.CagpuError("set_sensor_variants: the final record (keep_final) holds the rows the step kernel produced "
+                                 "under the primary sensor arguments; per-agent variants are rewritten on the host after the "
+                                 "launch and are not applied to it -- switch one of the two off")
         self._variants = []
         for mask, clip, sort in (variants or []):
             m = torch.from_numpy(np.array(np.broadcast_to(np.asarray(mask, bool), (self.E, self.N)))).to(self.device)
@@ -434,6 +444,8 @@ class BatchedSim(object):
             self._la["prep"] = None
         if table is None:
             self._ar, self._table = None, None
+            if self._fin_on:        # (no auto-reset, nothing is overwritten: the final record goes with the table)
+                self.keep_final(False)
             return
         t = self._dev(table, torch.float64)
         assert t.dim() == 3 and t.shape[1:] == (self.N, 6), t.shape
@@ -620,6 +632,9 @@ class BatchedSim(object):
         self._rewards = new(self._rewards); co.rewards = self._rewards.data_ptr()
         self._done = new(self._done); co.done = self._done.data_ptr()
         self._game_over = new(self._game_over); co.game_over = self._game_over.data_ptr()
+        if self._fin_on:   # (the final record handed out with those outputs belongs to their holder as well)
+            self._fin_obs, self._fin_flags = new(self._fin_obs), new(self._fin_flags)
+            self._cf.obs, self._cf.flags = self._fin_obs.data_ptr(), self._fin_flags.data_ptr()
 
     def step(self, ext_actions=None, ext_state=None):
         """ext_state: float64 [E, N, 5] = px, py, vx, vy, heading for agents with ExternalDynamics whose motion of THIS step
@@ -642,7 +657,12 @@ class BatchedSim(object):
             fa = self._fast_args
             if fa is None:
                 ar = None if self._ar is None else C.byref(self._ar)
-                if self._traj_on:
+                if self._fin_on:
+                    fa = (self.lib.cagpu_step_final, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
+                                                      C.byref(self._map) if (self._map is not None and self._maps is None) else None,
+                                                      None if self._maps is None else C.byref(self._maps),
+                                                      C.byref(self._ct) if self._traj_on else None, C.byref(self._cf)))
+                elif self._traj_on:
                     fa = (self.lib.cagpu_step_traj, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
                                                      C.byref(self._map) if (self._map is not None and self._maps is None) else None,
                                                      None if self._maps is None else C.byref(self._maps), C.byref(self._ct)))
@@ -678,7 +698,15 @@ class BatchedSim(object):
             e = self.ga3c(None if e is None else self._ga3c_ext)
         if self.fresh_outputs:
             self._new_outputs()
-        if self._traj_on:
+        if self._fin_on:
+            nat.check(self.lib.cagpu_step_final(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
+                                                None if e is None else e.data_ptr(),
+                                                None if self._ar is None else C.byref(self._ar),
+                                                C.byref(self._map) if (self._map is not None and self._maps is None) else None,
+                                                None if self._maps is None else C.byref(self._maps),
+                                                C.byref(self._ct) if self._traj_on else None, C.byref(self._cf),
+                                                self._stream()))
+        elif self._traj_on:
             nat.check(self.lib.cagpu_step_traj(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
                                                None if e is None else e.data_ptr(),
                                                None if self._ar is None else C.byref(self._ar),
@@ -714,7 +742,15 @@ class BatchedSim(object):
         e = self._dev(ext_actions, torch.float64)
         if self.fresh_outputs:
             self._new_outputs()
-        if self._traj_on:
+        if self._fin_on:   # (one block: it ends up holding every env's most recent terminal record of the launch)
+            chunk, ct = self._traj_chunk(int(n_steps)) if self._traj_on else (None, None)
+            nat.check(self.lib.cagpu_rollout_final(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
+                                                   None if e is None else e.data_ptr(),
+                                                   None if self._ar is None else C.byref(self._ar), int(n_steps), 0, 0,
+                                                   None if ct is None else C.byref(ct), C.byref(self._cf), self._stream()))
+            if chunk is not None:
+                self._traj_commit(chunk)
+        elif self._traj_on:
             chunk, ct = self._traj_chunk(int(n_steps))
             nat.check(self.lib.cagpu_rollout_traj(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
                                                   None if e is None else e.data_ptr(),
@@ -812,7 +848,17 @@ class BatchedSim(object):
         la["ring"] = prep["ring"]
         if not prep["in_kernel"]:
             la["snap"].copy_(self._slab)
-        if rec:               # the ring's own chunk of the tape: slot t of the launch records step t
+        la["fin_ring"] = prep["fin_ring"]
+        if prep["fin_ring"] is not None:   # the ring's final blocks (slot t: the envs that auto-reset in step t), tape or not
+            chunk, ct = self._traj_chunk(k, prep.get("traj")) if rec else (None, None)
+            rc = self.lib.cagpu_rollout_final(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, 1, prep["delta"],
+                                              None if ct is None else C.byref(ct), prep["cf_ref"],
+                                              _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
+            if rc != 0:
+                nat.check(rc)
+            if chunk is not None:
+                la["traj"] = self._traj_commit(chunk)
+        elif rec:             # the ring's own chunk of the tape: slot t of the launch records step t
             chunk, ct = self._traj_chunk(k, prep.get("traj"))
             rc = self.lib.cagpu_rollout_traj(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, 1, prep["delta"], C.byref(ct),
                                              _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
@@ -847,6 +893,13 @@ class BatchedSim(object):
         else:
             ring = la["ring"]           # (fresh=False: ONE persistent ring, a slot is overwritten k steps later)
         obs, rew, done, over = ring
+        fin_ring, cf = None, None
+        if self._fin_on:      # every slot carries its final block (rows valid where the slot's game_over is set)
+            fin_ring = la.get("fin_ring")
+            if la["fresh"] or fin_ring is None or fin_ring[0].shape[0] != k:
+                fin_ring = (torch.empty((k, E, N, self.W), dtype=torch.float32, device=dev),
+                            torch.empty((k, E, N), dtype=torch.int32, device=dev))
+            cf = nat.CaFinal(obs=fin_ring[0].data_ptr(), flags=fin_ring[1].data_ptr())
         co = nat.CaOut.from_buffer_copy(self._co)   # (the ring's own CaOut: the workspace of self._co, no actions / orca_vel record)
         co.actions, co.orca_vel = None, None
         co.obs, co.rewards, co.done, co.game_over = obs.data_ptr(), rew.data_ptr(), done.data_ptr(), over.data_ptr()
@@ -864,6 +917,7 @@ class BatchedSim(object):
         # (the kernels write 0 / 1 bytes: reinterpreted as bool without a conversion kernel)
         slots = list(zip(obs.unbind(0), rew.unbind(0), done.view(torch.bool).unbind(0), over.view(torch.bool).unbind(0)))
         return dict(k=k, key=key, ring=ring, co=co, co_ref=C.byref(co), ar_ref=ar_ref, in_kernel=in_kernel, slots=slots,
+                    fin_ring=fin_ring, cf=cf, cf_ref=None if cf is None else C.byref(cf),
                     traj=self._traj_alloc(k) if self._traj_on else None,   # (always its own tensors, fresh ring or not)
                     delta=(la["snap"].data_ptr() - self._slab.data_ptr()) if in_kernel else 0)
 
@@ -876,6 +930,16 @@ class BatchedSim(object):
             t = 0
         la["t"] = t + 1
         return la["slots"][t]
+
+    def lookahead_final(self):
+        """the final record of the slot step_lookahead() handed out last -> (final_obs [E,N,W], final_flags [E,N] int32),
+        views of the ring like the slot's outputs, WITHOUT a rewind (the `final_obs` / `final_flags` properties go through
+        sync() like `obs`); keep_final() must be on"""
+        la = self._la
+        if la is None or la["slots"] is None or la["t"] < 1 or la.get("fin_ring") is None:
+            return self.final_obs, self.final_flags
+        fo, ff = la["fin_ring"]
+        return fo[la["t"] - 1], ff[la["t"] - 1]
 
     def sync(self):
         """Make `state`, `obs`, `rewards`, `done`, `game_over` those of the step LAST HANDED OUT by step_lookahead (a no-op
@@ -893,8 +957,10 @@ class BatchedSim(object):
             if la["adaptive"]:     # the caller came back after t steps: that is how far the next ring looks ahead
                 la["cur"] = max(1, t)
                 la["streak"] = 0
+        fin_ring = la.get("fin_ring")
         if not la["fresh"]:
             la["ring"] = None      # (the current outputs below live in it: the next fill must not overwrite them)
+            la["fin_ring"] = None
         ch = la.pop("traj", None)
         if ch is not None and t < k:   # the tape keeps the t slots handed out; the replay below records nothing
             self._traj["bytes"] -= (k - t) * self.traj_step_bytes
@@ -905,11 +971,54 @@ class BatchedSim(object):
             co = self._co
             co.obs, co.rewards, co.done, co.game_over = (self._obs.data_ptr(), self._rewards.data_ptr(), self._done.data_ptr(),
                                                          self._game_over.data_ptr())
+            if fin_ring is not None and self._fin_on:   # ... and its final record the current one (the replay below keeps none)
+                self._fin_obs, self._fin_flags = own(fin_ring[0][t - 1]), own(fin_ring[1][t - 1])
+                self._cf.obs, self._cf.flags = self._fin_obs.data_ptr(), self._fin_flags.data_ptr()
         if t < k:
             self._slab.copy_(la["snap"])
             if t > 0:              # (rewrites slot t - 1 with the values it already holds)
                 nat.check(self.lib.cagpu_rollout(C.byref(self.p), C.byref(self._cs), C.byref(self._co), None,
                                                  None if self._ar is None else C.byref(self._ar), t, self._stream()))
+
+    # ---------------------------------------------------------------- the final record (include/cagpu.h CaFinal)
+    @property
+    def final_step_bytes(self):
+        """bytes the final record adds to one step's outputs (a ring slot): an observation block + a flag word per agent"""
+        return self.E * self.N * (4 * self.W + 4)
+
+    def keep_final(self, on=True):
+        """Keep, for every env that auto-resets in a step, what the reset overwrites: the observation rows of the terminal
+        step (`final_obs`, float32 [E, N, W] -- the vector-env APIs' final_observation / terminal_observation) and the
+        agents' flag words as that step left them (`final_flags`, int32 [E, N] bit patterns: nat.decode_flags names the
+        endings).  Stored by the step kernels themselves (cagpu_step_final / cagpu_rollout_final) through step(),
+        rollout() and step_lookahead() alike; state, outputs and statistics are bit-identical to a run without it.  Rows
+        are valid where `game_over` is set and UNSPECIFIED elsewhere.  After rollout(n) the record holds every env's most
+        recent ending of those n steps (valid for the last step where `game_over` is set).  Needs a fixture table
+        (set_fixture_table: without auto-reset nothing is overwritten, the terminal observation is `obs`); detaching the
+        table switches it off.  Not combined with per-agent sensor variants (set_sensor_variants): those rows are rewritten
+        on the host after the launch, the record holds what the kernel produced -- whichever comes second raises.  The
+        laser-scan / occupancy-grid tensors are computed by their own kernels on the post-reset state and are not part of
+        the record.  Off by default: a sim that never calls this runs the calls and kernels it ran before."""
+        self.sync()
+        on = bool(on)
+        if on and self._ar is None:
+            raise nat.CagpuError("keep_final: no fixture table attached (set_fixture_table): without auto-reset nothing is "
+                                 "overwritten -- the terminal observation is `obs`")
+        if on and self._variants:
+            raise nat.CagpuError("keep_final: per-agent sensor variants (set_sensor_variants) are rewritten on the host after "
+                                 "the launch and are not applied to the final record -- switch one of the two off")
+        if on and not self._fin_on:
+            self._fin_obs = torch.zeros((self.E, self.N, self.W), dtype=torch.float32, device=self.device)
+            self._fin_flags = torch.zeros((self.E, self.N), dtype=torch.int32, device=self.device)
+            self._cf.obs, self._cf.flags = self._fin_obs.data_ptr(), self._fin_flags.data_ptr()
+        self._fin_on = on
+        if not on:
+            self._fin_obs, self._fin_flags = None, None
+            self._cf.obs, self._cf.flags = None, None
+        self._fast_args = None
+        if self._la is not None:
+            self._la["prep"] = None   # (a prepared ring launch carries, or lacks, its final blocks)
+            self._la["fin_ring"] = None
 
     # ---------------------------------------------------------------- the trajectory tape (include/cagpu.h CaTraj)
     TRAJ_BLOCK_BYTES = 8 << 20   # step(): slots are taken from blocks of about this size (at most 64 slots), not a tensor per step

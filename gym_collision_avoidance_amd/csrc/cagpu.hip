@@ -89,6 +89,10 @@ struct KArgs {
   // are E N 12 doubles / E ints (the kernels derive them from p).
   double* traj_rows;
   int32_t* traj_ep;
+  // final record (cagpu_step_final / cagpu_rollout_final; nullptr everywhere else): block 0 of CaFinal.obs / CaFinal.flags.
+  // The blocks advance with the output ring (ring_obs / ring_agent: 0 unless every step keeps its outputs).
+  float* fin_obs;
+  uint32_t* fin_flags;
 };
 
 // One row of the trajectory tape (CaTraj): the reference's global_state_history row (agent.py:275-287) + its index.
@@ -1566,6 +1570,7 @@ LP1_UNROLL
               h0 = -kPi + kTwoPi * gen::uniform_at(k.heading_seed, static_cast<unsigned>(ge), static_cast<unsigned>(ge >> 32),
                                                    static_cast<unsigned>(reset_cnt), static_cast<unsigned>(a));
             }
+            if (k.fin_flags) k.fin_flags[i + ring_a] = r.flags;  // final record (CaFinal): the terminal step's flag word
             reset_lane(r, k.table + (c * N + a) * 6, k.heading_seed != 0, h0, p);
             // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by its agent 0 lane
             if (!MULTI && k.map_seed && a == 0) k.env_map[e] = map_draw(k.map_seed, k.env_id_offset + e, reset_cnt, k.num_maps);
@@ -1585,6 +1590,13 @@ LP1_UNROLL
       if (tid == 0 && again) wg_info |= 1ull << 16;
 #endif
       TICK(10);
+      // final record (CaFinal; workgroup-uniform tests): the terminal rows of the envs that reset, from where P4 / A3 left
+      // them (LDS when staged, else read back from the output rows: every wave's stores to them are drained first)
+      float* fin_tile = nullptr;
+      if (again && k.fin_obs) {
+        fin_tile = k.fin_obs + (obs_tile - k.o.obs);
+        if (!STAGE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
       if (RO && again) {
         __syncthreads();  // (full fence: the copy below overwrites observation rows other threads stored in P4)
         // ---- RO: the observation of a freshly reset env is a pure function of its fixture case: it was computed once
@@ -1599,6 +1611,7 @@ LP1_UNROLL
             float v = src[q];
             if (col == 0)  // (is_learning comes from the live flags; the row of an absent slot is all zeros: radius 0)
               v = ((sh_flag[le2 * N + a2] & CA_IS_LEARNING) && !(p.ragged && !(src[q + 5] > 0.f))) ? 1.f : 0.f;
+            if (fin_tile) fin_tile[base + q] = STAGE ? sh_obs[base + q] : obs_tile[base + q];  // (same thread, same element)
             if (STAGE) sh_obs[base + q] = v;
             else obs_tile[base + q] = v;
           }
@@ -1624,6 +1637,16 @@ LP1_UNROLL
           }
         }
         return 0;
+      }
+      if (fin_tile) {
+        // (no reset observations to copy: the second pass below overwrites the rows of the envs that reset -- every agent
+        // lane of such an env saves its own row first; the rare path: random headings, or a table without reset_obs)
+        __syncthreads();
+        if (wave0 && need_second) {
+          const float* src = (STAGE ? sh_obs : obs_tile) + __mul24(lane, W);
+          float* dst = fin_tile + __mul24(lane, W);
+          for (int q = 0; q < W; ++q) dst[q] = src[q];
+        }
       }
       return 1;  // some env of the tile auto-reset: run the sensing pass once more for it
     };
@@ -1825,6 +1848,8 @@ void ring_advance(KArgs& k) {
   if (k.o.orca_vel) k.o.orca_vel += 2 * k.ring_agent;
   if (k.traj_rows) k.traj_rows += static_cast<int64_t>(k.p.num_envs) * k.p.num_agents * 12;  // (a tape advances in a plain rollout too)
   if (k.traj_ep) k.traj_ep += k.p.num_envs;
+  if (k.fin_obs) k.fin_obs += k.ring_obs;        // (the final record advances with the outputs: not in a plain rollout)
+  if (k.fin_flags) k.fin_flags += k.ring_agent;
 }
 
 template <int NT, bool STAGE, int NC, bool MULTI, bool RO, int TE = 0>
@@ -1987,11 +2012,18 @@ int launch_pipe2(const KArgs& k0, hipStream_t st) {
     const long per_cu = (160 * 1024) / static_cast<long>(G::LDS) < 4 ? (160 * 1024) / static_cast<long>(G::LDS) : 4;
     if (grid > cus && grid <= per_cu * cus) k.yield_t = CAGPU_PIPE_YIELD_T;
   }
-  std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_pipe_kernel<%d, %d, %s> grid=%u lds=%zu mode=%d%s%s", NC, TE,
+  std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_pipe_kernel<%d, %d, %s> grid=%u lds=%zu mode=%d%s%s%s", NC, TE,
                 MULTI ? "true" : "false", grid, static_cast<size_t>(G::LDS), k.mode, k.yield_t > 0 ? " fair" : "",
-                k.traj_rows ? " traj" : "");
-  // (recording is a template flag: the instantiations without it are the code they were before the tape existed)
-  if (k.traj_rows) {
+                k.traj_rows ? " traj" : "", k.fin_obs ? " final" : "");
+  // (recording and the final record are template flags: the instantiations without them are the code they were before)
+  if (k.fin_obs) {
+    const bool fair = MULTI && k.yield_t > 0;
+    if (k.traj_rows) {
+      if (fair) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, MULTI, true, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+      else hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, false, true, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+    } else if (fair) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, MULTI, false, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+    else hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, false, false, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+  } else if (k.traj_rows) {
     if (MULTI && k.yield_t > 0) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, MULTI, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
     else hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, false, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
   } else if (MULTI && k.yield_t > 0) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, MULTI>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
@@ -2189,7 +2221,14 @@ static int check_map_set(const CaMapSet* set, const char* who) {
 static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const double* ext, const CaAutoReset* ar,
                      int32_t n_steps, void* stream, const CaMap* map = nullptr, const bool ring = false,
                      const int64_t snapshot_delta = 0, const bool query_snapshot = false, const CaMapSet* set = nullptr,
-                     const CaTraj* traj = nullptr, const bool want_traj = false) {
+                     const CaTraj* traj = nullptr, const bool want_traj = false, const CaFinal* fin = nullptr,
+                     const bool want_fin = false) {
+  if (want_fin) {  // (first, like the tape's: a bad final record is reported as such whatever else is wrong with the call)
+    if (!fin || !fin->obs) return fail(CA_EINVAL, "cagpu: NULL CaFinal or CaFinal.obs%s");
+    if ((reinterpret_cast<uintptr_t>(fin->obs) & 15u) || (reinterpret_cast<uintptr_t>(fin->flags) & 3u))
+      return fail(CA_EINVAL, "cagpu: CaFinal.obs must be 16-byte aligned (CaFinal.flags: 4-byte)%s");
+    if (!ar) return fail(CA_EINVAL, "cagpu: a CaFinal without a CaAutoReset (no auto-reset, nothing is overwritten)%s");
+  }
   if (want_traj) {  // (first: a bad tape is reported as such whatever else is wrong with the call)
     if (!traj || !traj->rows) return fail(CA_EINVAL, "cagpu: NULL CaTraj or CaTraj.rows%s");
     if ((reinterpret_cast<uintptr_t>(traj->rows) & 15u) || (reinterpret_cast<uintptr_t>(traj->episode) & 3u))
@@ -2225,6 +2264,7 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
   }
   k.n_steps = n_steps; k.mode = MODE_STEP;
   if (want_traj) { k.traj_rows = traj->rows; k.traj_ep = traj->episode; }
+  if (want_fin) { k.fin_obs = fin->obs; k.fin_flags = fin->flags; }
   k.inv_rvo_dt = 1.0 / p->rvo_dt;
   {
     static std::atomic<int> seq{0};
@@ -2278,6 +2318,20 @@ int cagpu_rollout_traj(const CaParams* p, const CaState* s, const CaOut* o, cons
                        int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj* traj, void* stream) {
   if (!ring && snapshot_delta != 0) return fail(CA_EINVAL, "cagpu_rollout_traj: snapshot_delta without ring%s");
   return step_impl(p, s, o, ext_actions, ar, n_steps, stream, nullptr, ring != 0, snapshot_delta, false, nullptr, traj, true);
+}
+
+int cagpu_step_final(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
+                     const CaMap* map, const CaMapSet* set, const CaTraj* traj, const CaFinal* fin, void* stream) {
+  if (map && set) return fail(CA_EINVAL, "cagpu_step_final: a CaMap and a CaMapSet at once%s");
+  return step_impl(p, s, o, ext_actions, ar, 1, stream, map, false, 0, false, set, traj, traj != nullptr, fin, true);
+}
+
+int cagpu_rollout_final(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
+                        int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj* traj, const CaFinal* fin,
+                        void* stream) {
+  if (!ring && snapshot_delta != 0) return fail(CA_EINVAL, "cagpu_rollout_final: snapshot_delta without ring%s");
+  return step_impl(p, s, o, ext_actions, ar, n_steps, stream, nullptr, ring != 0, snapshot_delta, false, nullptr, traj,
+                   traj != nullptr, fin, true);
 }
 
 static int laserscan_impl(const CaParams* p, const CaState* s, const CaMap* map, const CaScan* scan, void* stream,

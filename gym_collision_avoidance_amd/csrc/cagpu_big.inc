@@ -394,6 +394,12 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
           h0 = -kPi + kTwoPi * gen::uniform_at(k.heading_seed, static_cast<unsigned>(ge), static_cast<unsigned>(ge >> 32),
                                                static_cast<unsigned>(reset_cnt), static_cast<unsigned>(a));
         }
+        if (k.fin_obs) {  // final record (CaFinal): this thread's own terminal row and flag word, before the second pass
+          const float* src = k.o.obs + i * W;   // (one launch per step: the host advances the block with the outputs)
+          float* dst = k.fin_obs + i * W;
+          for (int q = 0; q < W; ++q) dst[q] = src[q];
+          if (k.fin_flags) k.fin_flags[i] = r.flags;
+        }
         reset_lane(r, k.table + (c * N + a) * 6, k.heading_seed != 0, h0, p);
         statics_dirty = true;
         do_sense = true;

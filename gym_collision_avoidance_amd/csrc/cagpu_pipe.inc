@@ -233,7 +233,10 @@ struct Geo {
 // TRAJ: the instantiation also records the trajectory tape (CaTraj, KArgs.traj_rows != nullptr).  A template flag and not
 // a uniform test: the programmes below are tuned down to their register counts, and the instantiations without the flag are
 // the code they were before the tape existed.
-template <int NC, int TE, bool MULTI, bool FAIR = false, bool TRAJ = false>
+// FINAL: the instantiation also keeps the final record (CaFinal, KArgs.fin_obs != nullptr) of the envs that auto-reset: wave 0
+// stores the terminal flag words in A4, the S-pair waves save the terminal rows in front of their reset-observation copy.
+// A template flag for the same reason.
+template <int NC, int TE, bool MULTI, bool FAIR = false, bool TRAJ = false, bool FINAL = false>
 __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
   static_assert(MULTI || !FAIR, "progress-fair priorities belong to the n-step kernel");
   using G = Geo<NC, TE>;
@@ -857,6 +860,8 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
           if (reset_here) {
             reset_cnt += 1;
             const long c = (k.env_id_offset + env0 + le + static_cast<long>(reset_cnt) * k.case_stride) % k.n_cases;
+            // final record (CaFinal): the flag word as the terminal step leaves it, in the slot of this step's outputs
+            if (FINAL && k.fin_flags) (k.fin_flags + out_base)[lane] = flags;
             Lane r;
             r.flags = flags;
             reset_lane(r, k.table + (c * N + a) * 6, false, 0.0, p);
@@ -1167,8 +1172,13 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
           if (!c1) continue;
           const float* src = k.reset_obs + static_cast<long>(c1 - 1) * N * W;
           float* dst = obs_tile + le2 * N * W;
+          // final record (CaFinal): the terminal rows are complete in the output block by now (the fences above: P4 of the
+          // three waves, A3 of wave 0) -- every lane saves the elements it is about to overwrite, in the block that advances
+          // with the output ring
+          float* fin = FINAL ? k.fin_obs + (dst - k.o.obs) : nullptr;
           for (int q = ts; q < N * W; q += S_PAIR) {
             const int a2 = q / W, col = q - a2 * W;
+            if (FINAL) fin[q] = dst[q];
             float v = src[q];
             if (col == 0)  // (is_learning comes from the live flags; the row of an absent slot is all zeros: radius 0)
               v = ((sh_flag[le2 * N + a2] & CA_IS_LEARNING) && !(ragged && !(src[q + 5] > 0.f))) ? 1.f : 0.f;

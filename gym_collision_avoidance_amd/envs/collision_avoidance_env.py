@@ -138,6 +138,7 @@ class CollisionAvoidanceEnv(Env):
         self._host_policies, self._host_by_env, self._groups = [], None, []
         self._host_dynamics, self._hostdyn_by_env, self._ext_state = [], None, None
         self._traj_req = None     # record_trajectories(): dict(max_bytes) while recording is asked for
+        self._final_req = False   # keep_final_observations()
 
     # ------------------------------------------------------------------ configuration (reference setters)
     def set_agents(self, agents):
@@ -257,7 +258,10 @@ class CollisionAvoidanceEnv(Env):
             self.episode_step_number += 1
             self._snap = self._obs_np = self._scan_np = None
             obs, rewards, done, over = sim.step_lookahead()
-            return obs, rewards, over, False, {"which_agents_done": done, "which_agents_learning": self._learning_info}
+            info = {"which_agents_done": done, "which_agents_learning": self._learning_info}
+            if sim._fin_on:
+                return obs, rewards, over, self._final_items(info, over, *sim.lookahead_final()), info
+            return obs, rewards, over, False, info
         if self._la_on:
             sim.sync()             # an action / another dt: the simulator has to stand at the step last handed out
         sim.p.dt = self.dt_nominal if dt is None else float(dt)
@@ -278,7 +282,11 @@ class CollisionAvoidanceEnv(Env):
             if self._learning_info is None:
                 self._learning_info = {a.id: a.policy.is_still_learning for a in self.agents}
             info = {"which_agents_done": self._out(sim.done.view(torch.bool)), "which_agents_learning": self._learning_info}
-            return self._out(sim.obs), self._out(sim.rewards), self._out(sim.game_over.view(torch.bool)), False, info
+            over = self._out(sim.game_over.view(torch.bool))
+            truncated = False
+            if sim._fin_on:
+                truncated = self._final_items(info, over, self._out(sim.final_obs), sim.final_flags)
+            return self._out(sim.obs), self._out(sim.rewards), over, truncated, info
         rewards = sim.rewards[0].double().cpu().numpy()
         done = sim.done[0].cpu().numpy().astype(bool)
         game_over = bool(sim.game_over[0].item())
@@ -437,6 +445,9 @@ class CollisionAvoidanceEnv(Env):
             sim.set_plugins(np.array(pol)[None], np.array(dyn)[None], np.array(isl)[None], np.array(stl)[None])
             sim.set_fixture_table(f["table"] if f["auto_reset"] else None, env_id_offset=f["env_id_offset"],
                                   case_stride=f["case_stride"], heading_seed=f["heading_seed"])
+            if self._final_req:    # (asked for before reset(), or the batch was rebuilt)
+                self._check_final()
+                sim.keep_final(True)
             idx = (np.arange(E) + f["env_id_offset"]) % len(f["table"])
             if hasattr(f["table"], "data_ptr"):
                 import torch
@@ -455,6 +466,8 @@ class CollisionAvoidanceEnv(Env):
             groups = [agents0]
             self._host_by_env, self._hostdyn_by_env = None, None
         else:
+            if self._final_req:
+                self._check_final()
             sim.set_fixture_table(None)
             groups = [g if g is not None else agents0 for g in per_env]
             ids, self._host_by_env, self._hostdyn_by_env = [], [], []
@@ -534,7 +547,8 @@ class CollisionAvoidanceEnv(Env):
         # the look-ahead ring (see __init__): every policy answered inside the step kernel, nothing between two steps
         ring = self.lookahead
         if ring is None:
-            slot_bytes = E * N * (4 * sim.W + 5) + E
+            # (with the final record every slot carries its final block as well: the same budget, a shorter ring)
+            slot_bytes = E * N * (4 * sim.W + 5) + E + (sim.final_step_bytes if sim._fin_on else 0)
             ring = int(min(self.LOOKAHEAD_MAX, max(8, self.LOOKAHEAD_BYTES // slot_bytes)))
         self._la_on = bool(E > 1 and ring > 0 and not nets and not host_any and not Config.USE_STATIC_MAP and
                            not any(a.policy.is_external for g in groups for a in g) and sim.lookahead_ok())
@@ -838,6 +852,62 @@ class CollisionAvoidanceEnv(Env):
             cache[e] = cur if cur is not None else [np.zeros((0, 11)) for _ in range(sim.N)]
         return cache[e][a]
 
+    # ------------------------------------------------------------------ final observations (core.BatchedSim.keep_final)
+    def keep_final_observations(self, on=True):
+        """Batched mode with on-device auto-reset (set_fixture_suite(..., auto_reset=True)): keep what an auto-reset
+        overwrites.  The observation step() returns for an env whose episode just ended is the RESET observation of its
+        next episode; with this switched on the `info` dict of step() / rollout() also carries
+          "final_observation": float32 device tensor [E, N, 6+7K], the observation of the terminal step -- the
+                               final_observation / terminal_observation of the Gymnasium / SB3 vector APIs;
+          "final_info":        {"at_goal", "in_collision", "ran_out_of_time"}: bool device tensors [E, N], the agents'
+                               Agent.is_at_goal / in_collision / ran_out_of_time as the terminal step left them
+        -- both meaningful ONLY for the envs with game_over set in that step (other rows are unspecified) -- and the fourth
+        return value becomes `truncated`, a bool device tensor [E]: the episode ended with no agent in collision and at
+        least one agent (of those present) out of time.  rollout(n) reports the items of its last step.  Stored by the
+        step kernels themselves: the look-ahead ring keeps serving step(None), a slot's ring memory grows by the record
+        (a default-length ring may be shorter).  The 'laserscan' / 'occupancy_grid' tensors are computed by their own
+        kernels on the post-reset state and are NOT part of the record.  Off (the default): step() returns exactly what
+        it did before -- False and the two `info` keys.  May be called before or after reset() and survives reset()."""
+        if not on:
+            self._final_req = False
+            if self._sim is not None and self._sim._fin_on:
+                self._sim.keep_final(False)
+                self._resize_ring()
+            return
+        self._final_req = True
+        self._check_final()
+        if self._sim is not None and not self._sim._fin_on:
+            self._sim.keep_final(True)
+            self._resize_ring()
+
+    def _check_final(self):
+        if self.num_envs <= 1:
+            raise ValueError("keep_final_observations() is for batched envs (num_envs > 1)")
+        if self._fixture is None and (self.default_agents is not None or self._sim is not None):
+            raise ValueError("keep_final_observations() needs the on-device auto-reset of set_fixture_suite(..., "
+                             "auto_reset=True): without it nothing is overwritten")
+        if self._fixture is not None and not self._fixture["auto_reset"]:
+            raise ValueError("keep_final_observations() with auto_reset=False: no env is ever reset on the device, the "
+                             "terminal observation is the one step() returns")
+
+    def _resize_ring(self):
+        """the default ring length follows the bytes of a slot (see _upload): recomputed when the final record is toggled"""
+        sim = self._sim
+        if not self._la_on or self.lookahead is not None:
+            return
+        slot_bytes = self.num_envs * sim.N * (4 * sim.W + 5) + self.num_envs + (sim.final_step_bytes if sim._fin_on else 0)
+        sim.enable_lookahead(int(min(self.LOOKAHEAD_MAX, max(8, self.LOOKAHEAD_BYTES // slot_bytes))),
+                             fresh=not self.zero_copy, adaptive=True)
+
+    def _final_items(self, info, over, final_obs, final_flags):
+        """adds "final_observation" / "final_info" to `info` -> truncated [E] (a few elementwise device ops, no sync)"""
+        d = nat.decode_flags(final_flags)
+        present = ~d["absent"]
+        info["final_observation"] = final_obs
+        info["final_info"] = {"at_goal": d["at_goal"] & present, "in_collision": d["in_collision"],
+                              "ran_out_of_time": d["ran_out_of_time"] & present}
+        return over & ~d["in_collision"].any(dim=1) & info["final_info"]["ran_out_of_time"].any(dim=1)
+
     # ------------------------------------------------------------------ batched extras
     def rollout(self, n_steps):
         """n_steps x `step(None)` in ONE launch (`cagpu_rollout`): the device-side form of env_utils.run_episode's
@@ -861,7 +931,10 @@ class CollisionAvoidanceEnv(Env):
                 {a.id: bool(d) for a, d in zip(self.agents, sim.done[0].cpu().numpy())},
                 "which_agents_learning": {a.id: a.policy.is_still_learning for a in self.agents}}
         if self.num_envs > 1:
-            return self._out(sim.obs), self._out(sim.rewards), sim.game_over.bool(), False, info
+            over, truncated = sim.game_over.bool(), False
+            if sim._fin_on:   # (the last step's: the record holds every env's most recent ending of the n steps)
+                truncated = self._final_items(info, over, self._out(sim.final_obs), sim.final_flags)
+            return self._out(sim.obs), self._out(sim.rewards), over, truncated, info
         return self._get_obs(), sim.rewards[0].double().cpu().numpy(), bool(sim.game_over[0].item()), False, info
 
     def episode_stats(self):

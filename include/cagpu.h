@@ -182,7 +182,8 @@ typedef struct CaOut {
 /* Fixture-table auto-reset (the batched form of vec_env.py:120-128 + test_cases.py:593-624):
  * when env e's episode ends its statistics are added to env_stats[e], its k-th reset loads case
  * (env_id_offset + e + k*case_stride) % n_cases of `table` and the observation handed back is the
- * reset observation (rewards / done / game_over stay those of the terminal step). */
+ * reset observation (rewards / done / game_over stay those of the terminal step; the terminal observation and the
+ * agents' final flag words are kept on request: CaFinal, cagpu_step_final / cagpu_rollout_final). */
 typedef struct CaAutoReset {
   const double *table; /* device, [n_cases, N, 6] = px, py, gx, gy, pref_speed, radius */
   int32_t n_cases;
@@ -264,6 +265,23 @@ typedef struct CaTraj {
   double  *rows;     /* device [n_steps, E, N, 12], 16-byte aligned */
   int32_t *episode;  /* device [n_steps, E] or NULL: CaState.reset_count[e] as the step STARTS (before its auto-reset) */
 } CaTraj;
+
+/* Final record of cagpu_step_final / cagpu_rollout_final: what an auto-reset would otherwise overwrite.  For every env whose
+ * episode ends in a step AND is auto-reset in it (game_over[e] != 0 with a CaAutoReset attached), the step kernel stores,
+ * before the reset replaces them,
+ *   obs    the env's observation rows of the TERMINAL step, exactly as the step produced them (is_learning column included;
+ *          the rows of absent slots are zeros) -- the `final_observation` / `terminal_observation` of the vector-env APIs;
+ *   flags  the agents' flag words as they stand at the end of the terminal step (CA_AT_GOAL / CA_IN_COLLISION /
+ *          CA_OUT_OF_TIME / CA_DONE / CA_ABSENT ... as decided by that step; CA_PLAN_VALID is unspecified).
+ * Rows of every OTHER env are LEFT ALONE (whatever the caller's buffer held): a row is valid where game_over says so.
+ * Slots: the block advances exactly as the CaOut outputs do -- a ring call (every step keeps its outputs) writes step t's
+ * records to block t of [n_steps, E, N, 6+7K] / [n_steps, E, N]; a plain cagpu_rollout_final (ring == 0: every step writes
+ * the same CaOut buffers) writes every step's records to the SAME single block, which therefore ends up holding each env's
+ * MOST RECENT terminal record of the launch (envs that ended no episode in it keep what the buffer held). */
+typedef struct CaFinal {
+  float    *obs;    /* device [E, N, 6+7K] (ring: [n_steps, E, N, 6+7K]), the layout of CaOut.obs; 16-byte aligned */
+  uint32_t *flags;  /* device [E, N] (ring: [n_steps, E, N]) or NULL; 4-byte aligned */
+} CaFinal;
 
 /* GA3C-CADRL network weights (policies/GA3C_CADRL/checkpoints/<run>/network_*.data-00000-of-00001): device float
  * pointers in the checkpoint's own layout, kernels row-major [in, out].  LSTM gate order i, j, f, o. */
@@ -456,6 +474,19 @@ int cagpu_step_traj(const CaParams *p, const CaState *s, const CaOut *o, const d
                     const CaMap *map, const CaMapSet *set, const CaTraj *traj, void *stream);
 int cagpu_rollout_traj(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                        int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj *traj, void *stream);
+
+/* The step / rollout calls that also keep the FINAL RECORD (CaFinal) of every env that auto-resets, and -- `traj` may be
+ * NULL -- record the trajectory tape as well: cagpu_step_traj / cagpu_rollout_traj with one more argument, the same kernel
+ * selection, grid and block; state, outputs, statistics (and the tape) are bit-identical to the calls they mirror.  Every
+ * kernel that auto-resets keeps the record: the pipelined kernels (a template flag: cagpu_last_kernel() shows " final"
+ * behind the name), the general kernel on both of its reset paths (reset_obs copy / second sensing pass) and the large-env
+ * kernel.  CA_EINVAL, nothing launched: fin or fin->obs NULL, fin->obs not 16-byte / fin->flags not 4-byte aligned, fin
+ * without ar (nothing is ever overwritten then) -- plus whatever the mirrored call rejects. */
+int cagpu_step_final(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
+                     const CaMap *map, const CaMapSet *set, const CaTraj *traj, const CaFinal *fin, void *stream);
+int cagpu_rollout_final(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
+                        int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj *traj, const CaFinal *fin,
+                        void *stream);
 
 /* The policy query of the NEXT step ahead of time (collision_avoidance_env.py:305-323 for the built-in RVO policy):
  * fills s->next_action from the CURRENT state and sets CA_PLAN_VALID, without stepping.  cagpu_step / cagpu_rollout keep
