@@ -81,6 +81,15 @@ class CaFinal(C.Structure):
     _fields_ = [("obs", _P), ("flags", _P)]
 
 
+class CaRender(C.Structure):
+    _fields_ = [("out", _P), ("num_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("flags", C.c_int32),
+                ("xmin", C.c_double), ("ymax", C.c_double), ("s16", C.c_double), ("frame_env", _P), ("frame_col", _P),
+                ("first", _P), ("last", _P), ("hist", _P), ("hist_steps", C.c_int32), ("hist_cols", C.c_int32),
+                ("stride_t", C.c_int64), ("stride_s", C.c_int64), ("work", _P), ("work_bytes", C.c_uint64)]
+
+
+RENDER_CIRCLES, RENDER_MAP = 1, 2   # CaRender.flags
+
 NET_FIELDS = ("lstm_kernel", "lstm_bias", "layer1_kernel", "layer1_bias", "layer2_kernel", "layer2_bias", "fc1_kernel",
               "fc1_bias", "logits_kernel", "logits_bias", "input_mean", "input_std")
 
@@ -94,7 +103,8 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_orca", "cagpu_observe", "cagpu_laserscan", "cagpu_ga3c", "cagpu_generate_cases", "cagpu_generate_cases_ragged", "cagpu_plan", "cagpu_debug_libm", "cagpu_device_faults", "cagpu_workspace_bytes",
            "cagpu_ga3c_packed_bytes", "cagpu_ga3c_pack", "cagpu_rollout_ring", "cagpu_ring_snapshots", "cagpu_debug_copy8", "cagpu_device_faults_async",
            "cagpu_step_maps", "cagpu_laserscan_maps", "cagpu_occupancy_grid", "cagpu_occupancy_grid_maps",
-           "cagpu_step_traj", "cagpu_rollout_traj", "cagpu_step_final", "cagpu_rollout_final")
+           "cagpu_step_traj", "cagpu_rollout_traj", "cagpu_step_final", "cagpu_rollout_final",
+           "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes")
 
 _lib = None
 
@@ -137,6 +147,10 @@ def lib():
                                    C.POINTER(CaFinal), _P]
     L.cagpu_rollout_final.argtypes = [PP, PS, PO, _P, PA, C.c_int32, C.c_int32, C.c_int64, C.POINTER(CaTraj),
                                       C.POINTER(CaFinal), _P]
+    L.cagpu_render.argtypes = [PP, PS, C.POINTER(CaMap), C.POINTER(CaRender), _P]
+    L.cagpu_render_maps.argtypes = [PP, PS, C.POINTER(CaMapSet), C.POINTER(CaRender), _P]
+    L.cagpu_render_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.cagpu_render_work_bytes.restype = C.c_uint64
     L.cagpu_observe.argtypes = [PP, PS, PO, _P]
     L.cagpu_plan.argtypes = [PP, PS, _P]
     L.cagpu_orca.argtypes = [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int32,
@@ -155,7 +169,8 @@ def lib():
     L.cagpu_debug_libm.argtypes = [C.c_int32, C.c_int32, _P, _P, _P, _P]
     for n in EXPORTS:
         getattr(L, n)  # AttributeError if a declared symbol is missing
-        if n not in ("cagpu_last_error", "cagpu_last_kernel", "cagpu_workspace_bytes", "cagpu_ga3c_packed_bytes"):
+        if n not in ("cagpu_last_error", "cagpu_last_kernel", "cagpu_workspace_bytes", "cagpu_ga3c_packed_bytes",
+                     "cagpu_render_work_bytes"):
             getattr(L, n).restype = C.c_int
     L.cagpu_last_error.restype = C.c_char_p
     L.cagpu_last_kernel.restype = C.c_char_p

@@ -1138,6 +1138,128 @@ class BatchedSim(object):
         return {"rows": torch.cat([sl(c, c["rows"]) for c in cs]), "episode": torch.cat([sl(c, c["ep"]) for c in cs]),
                 "epoch": torch.cat([c["epoch"].unsqueeze(0).expand(c["n"], E) for c in cs])}
 
+    # ---------------------------------------------------------------- frames (include/cagpu.h CaRender)
+    RENDER_WORK_BYTES = 256 << 20   # frames are rendered in groups whose primitive lists fit this much scratch
+
+    def _render_counters(self, ids, every=False):
+        """the tape's counters of the envs `ids` (device int64 [S]; every: all envs in order, nothing to gather)
+        -> episode [T, S], epoch [T, S], 4 bytes per env and slot each"""
+        tr = self._traj
+        cs = [] if tr is None else [c for c in tr["chunks"] if c["n"] > 0]
+        S = int(ids.shape[0])
+        if not cs:
+            none = torch.empty((0, S), dtype=torch.int32, device=self.device)
+            return none, none
+        pick = (lambda t, d: t) if every else (lambda t, d: t.index_select(d, ids))
+        ep = [pick(c["ep"][c["start"]:c["start"] + c["n"]], 1) for c in cs]
+        epoch = [pick(c["epoch"], 0).unsqueeze(0).expand(c["n"], S) for c in cs]
+        return (ep[0], epoch[0]) if len(cs) == 1 else (torch.cat(ep), torch.cat(epoch))
+
+    def _render_rows(self, ids, t0, t1, every=False):
+        """the slots [t0, t1) of the tape of the envs `ids` as one history block -> rows [t1 - t0, S, N, 12], gathered on
+        the device from the chunks that overlap the range only; a range inside one chunk with every env in order is a
+        VIEW of the tape, not a copy (the launch reads it through its strides)"""
+        pieces, base = [], 0
+        for c in self._traj["chunks"]:
+            a, b = max(t0, base), min(t1, base + c["n"])
+            if a < b:
+                t = c["rows"][c["start"] + a - base:c["start"] + b - base]
+                pieces.append(t if every else t.index_select(1, ids))
+            base += c["n"]
+        return pieces[0] if len(pieces) == 1 else torch.cat(pieces)
+
+    def _render_launch(self, frame_env, frame_col, first, last, rows, size, limits, circles, draw_map):
+        """F frames from device int32 [F] descriptors and a history block [T, S, N, 12] (or None) -> uint8 [F, H, W, 3]"""
+        from . import render as rd
+        H, W = int(size[0]), int(size[1])
+        xmin, ymax, s16 = rd.window((H, W), limits)
+        F = int(frame_env.shape[0])
+        T = 0 if rows is None else int(rows.shape[0])
+        per = int(self.lib.cagpu_render_work_bytes(1, self.N, T))
+        group = max(1, min(F, self.RENDER_WORK_BYTES // per))
+        work = torch.empty((int(self.lib.cagpu_render_work_bytes(group, self.N, T)),), dtype=torch.uint8, device=self.device)
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        frame_env, frame_col, first, last = i32(frame_env), i32(frame_col), i32(first), i32(last)
+        flags = (nat.RENDER_CIRCLES if circles else 0) | (nat.RENDER_MAP if draw_map else 0)
+        outs = []
+        for f0 in range(0, F, group):
+            n = min(group, F - f0)
+            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+            r = nat.CaRender(out=out.data_ptr(), num_frames=n, height=H, width=W, flags=flags, xmin=xmin, ymax=ymax, s16=s16,
+                             frame_env=frame_env[f0:].data_ptr(), frame_col=frame_col[f0:].data_ptr(),
+                             first=first[f0:].data_ptr(), last=last[f0:].data_ptr(),
+                             hist=None if rows is None else rows.data_ptr(), hist_steps=T,
+                             hist_cols=0 if rows is None else int(rows.shape[1]),
+                             stride_t=0 if rows is None else int(rows.stride(0)), stride_s=0 if rows is None else int(rows.stride(1)),
+                             work=work.data_ptr(), work_bytes=work.numel())
+            if self._maps is not None:
+                nat.check(self.lib.cagpu_render_maps(C.byref(self.p), C.byref(self._cs), C.byref(self._maps), C.byref(r),
+                                                     self._stream()))
+            else:
+                nat.check(self.lib.cagpu_render(C.byref(self.p), C.byref(self._cs),
+                                                None if self._map is None else C.byref(self._map), C.byref(r), self._stream()))
+            outs.append(out)
+        # (torch's caching allocator keeps a freed block for the stream that used it: the scratch tensors may go out of scope)
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    def render_frames(self, env_ids=None, size=(128, 128), limits=None, episode="current", upto=None, circles_along_traj=True,
+                      draw_map=True):
+        """One picture per env of `env_ids` (default: all), rasterised on the device (cagpu_render, csrc/cagpu_render.inc;
+        the reference's visualize.plot_episode minus text and axes): uint8 device tensor [S, H, W, 3], size = (H, W), showing
+        the window `limits` = ((xmin, xmax), (ymin, ymax)) (default: the 16 m x 16 m map extent) at equal scale.
+        episode="current": the running episode of each env as the trajectory tape holds it (record_trajectories);
+        "last": the most recent episode BEFORE the running one that the tape holds -- what the reference plots at the reset
+        that follows an episode; upto=k: the episode as of its k-th recorded step.  An env whose episode has no slot on the
+        tape (recording off, right after a reset, no earlier episode) gets a SNAPSHOT frame: the current state, one disc
+        per agent and its goal.  The history is gathered from the tape's chunks and the episode boundaries are found from
+        the tape's counters on the device: no tape row and no state travels to the host (two integers do: the bounds of
+        the tape window that the frames show, so that only its slots are gathered and the scratch is sized by it).  Goes
+        through sync(); writes nothing of the simulator."""
+        from . import render as rd
+        self.sync()
+        ids = torch.arange(self.E, device=self.device) if env_ids is None else \
+            torch.as_tensor(env_ids, dtype=torch.int64).reshape(-1).to(self.device)
+        every = env_ids is None
+        ep, epoch = self._render_counters(ids, every)
+        cur_epoch = torch.zeros((self.E,), dtype=torch.int32, device=self.device) if self._traj is None else self._traj["epoch"]
+        first, last = rd.episode_ranges(ep, epoch, self._state["reset_count"].index_select(0, ids),
+                                        cur_epoch.index_select(0, ids), episode, upto)
+        rows, T = None, int(ep.shape[0])
+        if T > 0:
+            # the window of the tape that some frame shows (two integers read back): only its slots are gathered, and the
+            # primitive lists are sized by it, not by the whole tape
+            has = last >= first
+            t0, t1 = torch.stack([torch.where(has, first, torch.full_like(first, T)).min(),
+                                  torch.where(has, last, torch.full_like(last, -1)).max()]).tolist()
+            if t1 >= t0:
+                rows = self._render_rows(ids, t0, t1 + 1, every)
+                first, last = first - t0, last - t0
+        return self._render_launch(ids, torch.arange(int(ids.shape[0]), device=self.device), first, last, rows, size, limits,
+                                   circles_along_traj, draw_map)
+
+    def render_episode(self, env_id, episode="last", every=1, size=(128, 128), limits=None, circles_along_traj=True,
+                       draw_map=True):
+        """The animation of ONE episode of env `env_id` from ONE launch: uint8 device tensor [F, H, W, 3], frame j showing
+        the episode's first (j + 1) * every recorded steps, the last frame all of them (render_frames(upto=...) of the same
+        prefixes, bit for bit).  Only the episode's LENGTH is read back (two integers) to size the output; with no such
+        episode on the tape the result is one snapshot frame."""
+        from . import render as rd
+        self.sync()
+        ids = torch.as_tensor([int(env_id)], dtype=torch.int64, device=self.device)
+        ep, epoch = self._render_counters(ids)
+        cur_epoch = torch.zeros((self.E,), dtype=torch.int32, device=self.device) if self._traj is None else self._traj["epoch"]
+        first, last = rd.episode_ranges(ep, epoch, self._state["reset_count"].index_select(0, ids),
+                                        cur_epoch.index_select(0, ids), episode)
+        f0, l0 = int(first[0]), int(last[0])
+        lasts = rd.prefix_lasts(l0 - f0 + 1, every)
+        if not lasts:
+            return self._render_launch(ids, torch.zeros_like(ids), first, last, None, size, limits, circles_along_traj, draw_map)
+        rows = self._render_rows(ids, f0, l0 + 1)       # (the episode's slots only: the primitive lists are sized by the block)
+        F = len(lasts)
+        zero = torch.zeros((F,), dtype=torch.int32, device=self.device)
+        return self._render_launch(ids.expand(F), zero, zero, torch.as_tensor(lasts, dtype=torch.int32, device=self.device), rows,
+                                   size, limits, circles_along_traj, draw_map)
+
     # ---------------------------------------------------------------- statistics
     def _fault_probe(self):
         """The device's fault word on the product path, without a synchronisation: a 4-byte copy into pinned host memory

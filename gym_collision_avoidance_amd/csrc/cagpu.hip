@@ -624,6 +624,7 @@ __device__ unsigned long long g_wgtime[4096 * 8];
 __host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
 #include "cagpu_scan.inc"
 #include "cagpu_occ.inc"
+#include "cagpu_render.inc"
 #include "cagpu_ga3c.inc"
 #include "cagpu_gen.inc"
 
@@ -2413,6 +2414,68 @@ int cagpu_occupancy_grid_maps(const CaParams* p, const CaState* s, const CaMapSe
   const int rc = check_map_set(set, "cagpu_occupancy_grid_maps");
   if (rc) return rc;
   return occupancy_impl(p, s, &set->map, g, stream, set);
+}
+
+static int render_impl(const CaParams* p, const CaState* s, const CaMap* map, const CaRender* r, void* stream,
+                       const CaMapSet* set = nullptr) {
+  if (!p || !s || !r) return fail(CA_EINVAL, "cagpu_render: NULL argument%s");
+  if (p->num_envs < 1 || p->num_agents < 1 || p->num_agents > big::NT_MAX) return fail(CA_EINVAL, "cagpu_render: bad sizes%s");
+  if (!s->pos_x || !s->pos_y || !s->goal_x || !s->goal_y || !s->radius || !s->flags)
+    return fail(CA_EINVAL, "cagpu_render: NULL state pointer%s");
+  if (!r->out || (reinterpret_cast<uintptr_t>(r->out) & 15)) return fail(CA_EINVAL, "cagpu_render: output NULL or not 16-byte aligned%s");
+  if (r->num_frames < 1 || r->height < 16 || r->height > 1024 || r->width < 16 || r->width > 1024)
+    return fail(CA_EINVAL, "cagpu_render: num_frames < 1, or height / width outside [16, 1024]%s");
+  if (!(r->s16 > 0.0) || !(r->s16 <= 1e9) || !(r->xmin - r->xmin == 0.0) || !(r->ymax - r->ymax == 0.0))
+    return fail(CA_EINVAL, "cagpu_render: bad window (xmin, ymax must be finite, 0 < s16 <= 1e9)%s");
+  if (!r->frame_env || !r->first || !r->last) return fail(CA_EINVAL, "cagpu_render: NULL frame_env / first / last%s");
+  if (r->hist_steps < 0 || (r->hist_steps > 0 && (!r->hist || r->hist_cols < 1 || r->stride_s < 0 || r->stride_t < 0)))
+    return fail(CA_EINVAL, "cagpu_render: bad history block%s");
+  if (r->hist && (reinterpret_cast<uintptr_t>(r->hist) & 15)) return fail(CA_EINVAL, "cagpu_render: history not 16-byte aligned%s");
+  const bool has_map = map && map->static_bits;
+  if (has_map && (map->rows < 1 || map->cols < 1 || !(map->cell > 0.0))) return fail(CA_EINVAL, "cagpu_render: bad CaMap%s");
+  const int T = r->hist ? r->hist_steps : 0;
+  if (render_cap(p->num_agents, T) > 0x7FFFFFFFu) return fail(CA_EUNSUPPORTED, "cagpu_render: too many history rows per frame%s");
+  if (!r->work || (reinterpret_cast<uintptr_t>(r->work) & 15) || r->work_bytes < render_work_bytes(r->num_frames, p->num_agents, T))
+    return fail(CA_EINVAL, "cagpu_render: workspace NULL, not 16-byte aligned or smaller than cagpu_render_work_bytes()%s");
+  RenderArgs k;
+  std::memset(&k, 0, sizeof(k));
+  k.p = *p; k.s = *s; k.r = *r;
+  if (has_map) k.m = *map;
+  if (!r->hist) k.r.hist_steps = 0;
+  if (set) { k.env_map = set->env_map; k.num_maps = set->num_maps; }
+  k.cap = static_cast<int32_t>(render_cap(p->num_agents, T));
+  const int u = r->width > r->height ? r->width : r->height;
+  k.g16 = (291 * u) / 1000 < 32 ? 32 : (291 * u) / 1000;
+  k.d16 = (108 * u) / 1000 < 16 ? 16 : (108 * u) / 1000;
+  k.tiles_x = (r->width + RD_TW - 1) / RD_TW;
+  k.tiles_y = (r->height + RD_TH - 1) / RD_TH;
+  const long blocks = static_cast<long>(k.tiles_x) * k.tiles_y * r->num_frames;
+  if (blocks > 0x7FFFFFFFL) return fail(CA_EUNSUPPORTED, "cagpu_render: more than 2^31 - 1 (frame, tile) workgroups%s");
+  const int N = p->num_agents;
+  const size_t lds = static_cast<size_t>(N) * (8 + 7 * 4) + 8 + 16;
+  hipLaunchKernelGGL(render_prep_kernel, dim3(static_cast<unsigned>(r->num_frames)), dim3(RD_NT), lds,
+                     static_cast<hipStream_t>(stream), k);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(render_raster_kernel, dim3(static_cast<unsigned>(blocks)), dim3(RD_NT), 0, static_cast<hipStream_t>(stream), k);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
+}
+
+uint64_t cagpu_render_work_bytes(int32_t num_frames, int32_t num_agents, int32_t hist_steps) {
+  if (num_frames < 1 || num_agents < 1 || hist_steps < 0) return 0;
+  return render_work_bytes(num_frames, num_agents, hist_steps);
+}
+
+int cagpu_render(const CaParams* p, const CaState* s, const CaMap* map, const CaRender* r, void* stream) {
+  return render_impl(p, s, map, r, stream);
+}
+
+int cagpu_render_maps(const CaParams* p, const CaState* s, const CaMapSet* set, const CaRender* r, void* stream) {
+  const int rc = check_map_set(set, "cagpu_render_maps");
+  if (rc) return rc;
+  return render_impl(p, s, &set->map, r, stream, set);
 }
 
 int cagpu_ga3c(const CaParams* p, const CaState* s, const float* obs, const CaNet* net, double* ext_actions, float* logits,

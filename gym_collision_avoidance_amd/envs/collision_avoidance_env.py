@@ -12,7 +12,7 @@ backed by the batched HIP simulator.
 Everything `step` computes (policy queries, dynamics, collisions, rewards, sensors, done flags; reference lines
 156-234, 284-327, 394-575) happens in ONE launch of the fused kernel (csrc/cagpu.hip).  The host only translates the
 reference's call conventions: the actions dict, the nested observation dict, the info dicts keyed by agent.id.
-Out of scope here: plotting / animation, static maps and map-based sensors.
+Out of scope here: static maps and map-based sensors.
 """
 import copy
 import inspect
@@ -94,7 +94,7 @@ class CollisionAvoidanceEnv(Env):
         self.collision_dist = Config.COLLISION_DIST
         self.getting_close_range = Config.GETTING_CLOSE_RANGE
         self.evaluate = Config.EVALUATE_MODE
-        self.plot_episodes = False  # plotting is host-side tooling, out of scope
+        self.plot_episodes = False  # nothing plots by itself: render() / render_episode() / save_episode_plots() on request
         self.test_case_index = 0
         self.set_testcase(Config.TEST_CASE_FN, dict(Config.TEST_CASE_ARGS))
         # action bounds (collision_avoidance_env.py:86-109)
@@ -216,7 +216,7 @@ class CollisionAvoidanceEnv(Env):
         self.static_map_filename = static_map
 
     def set_plot_save_dir(self, plot_save_dir):
-        self.plot_save_dir = plot_save_dir  # accepted and ignored: no plotting here
+        self.plot_save_dir = plot_save_dir  # the default directory of save_episode_plots(); step() / reset() never plot
 
     def set_perturbed_info(self, perturbed_obs):
         self.perturbed_obs = perturbed_obs
@@ -851,6 +851,67 @@ class CollisionAvoidanceEnv(Env):
                     cur = self.episode_histories(e)[-1]
             cache[e] = cur if cur is not None else [np.zeros((0, 11)) for _ in range(sim.N)]
         return cache[e][a]
+
+    # ------------------------------------------------------------------ frames (core.BatchedSim.render_frames)
+    def _render_defaults(self, kw):
+        kw.setdefault("limits", Config.PLT_LIMITS)
+        kw.setdefault("circles_along_traj", bool(Config.PLOT_CIRCLES_ALONG_TRAJ))
+        return kw
+
+    def render(self, mode="rgb_array", env_ids=None, **kw):
+        """Frames of the episodes, rasterised on the device (core.BatchedSim.render_frames: the reference's
+        visualize.plot_episode minus text and axes; keywords size=(H, W), limits, episode="current" | "last", upto,
+        circles_along_traj, draw_map -- limits / circles_along_traj default to Config.PLT_LIMITS /
+        PLOT_CIRCLES_ALONG_TRAJ).  num_envs == 1: the uint8 numpy array [H, W, 3] Gym's "rgb_array" mode returns; batched:
+        the uint8 device tensor [S, H, W, 3] of `env_ids` (default: all envs).  Trajectories appear where the tape
+        records them (record_trajectories()); without it a frame shows the current state."""
+        if mode != "rgb_array":
+            raise NotImplementedError("render(mode=%r): there is no window to draw into here -- use mode='rgb_array' (frames "
+                                      "as arrays) or save_episode_plots() (PNG / GIF files)" % (mode,))
+        if self._sim is None:
+            raise RuntimeError("call reset() before render()")
+        frames = self._sim.render_frames(env_ids, **self._render_defaults(kw))
+        return frames[0].cpu().numpy() if self.num_envs == 1 else frames
+
+    def render_episode(self, env_id=0, episode="last", every=1, **kw):
+        """the animation frames of one episode of one env, uint8 device tensor [F, H, W, 3], from one launch
+        (core.BatchedSim.render_episode)"""
+        if self._sim is None:
+            raise RuntimeError("call reset() before render_episode()")
+        return self._sim.render_episode(env_id, episode=episode, every=every, **self._render_defaults(kw))
+
+    def save_episode_plots(self, env_ids=None, directory=None, animate=False, episode="current", **kw):
+        """Write the episode plots of `env_ids` (default: all) as files, named like the reference's
+        (visualize.py:27-38, :138-149): `{test_case:03d}_{policy}_{num_agents}agents.png` in `directory` (default: the one
+        given to set_plot_save_dir), a copy under `collisions/` where some agent of the env is in collision, and with
+        `animate` a GIF of render_episode()'s frames under `animations/`.  test_case = test_case_index (+ the env's index
+        in a batch), policy = plot_policy_name or the first agent's policy name.  The collision test reads the CURRENT
+        flag words: use it with episode="current" before the env is reset (episode="last" plots the finished episode
+        but cannot know how it ended).  Encoded by PIL.  Returns the list of PNG paths.  Nothing plots unless this is
+        called: Config.SAVE_EPISODE_PLOTS / ANIMATE_EPISODES have no effect on step() / reset()."""
+        import os
+        from gym_collision_avoidance_amd import render as rd
+        if self._sim is None:
+            raise RuntimeError("call reset() before save_episode_plots()")
+        directory = self.plot_save_dir if directory is None else directory
+        if directory is None:
+            raise ValueError("save_episode_plots: no directory given and none set with set_plot_save_dir()")
+        ids = list(range(self.num_envs)) if env_ids is None else [int(e) for e in np.asarray(env_ids).reshape(-1)]
+        kw = self._render_defaults(kw)
+        frames = self._sim.render_frames(ids, episode=episode, **kw).cpu().numpy()
+        flags = self._sim.state["flags"][ids].cpu().numpy()
+        policy = self.plot_policy_name or self.agents[0].policy.str
+        paths = []
+        for j, e in enumerate(ids):
+            present = (flags[j] & nat.ABSENT) == 0
+            name = "%03d_%s_%dagents" % (self.test_case_index + e, policy, int(present.sum()))
+            paths.append(rd.save_frames(os.path.join(directory, name + ".png"), frames[j]))
+            if ((flags[j] & nat.IN_COLLISION) != 0)[present].any():
+                rd.save_frames(os.path.join(directory, "collisions", name + ".png"), frames[j])
+            if animate:
+                anim = self._sim.render_episode(e, episode=episode, **kw).cpu().numpy()
+                rd.save_frames(os.path.join(directory, "animations", name + ".gif"), anim)
+        return paths
 
     # ------------------------------------------------------------------ final observations (core.BatchedSim.keep_final)
     def keep_final_observations(self, on=True):

@@ -283,6 +283,33 @@ typedef struct CaFinal {
   uint32_t *flags;  /* device [E, N] (ring: [n_steps, E, N]) or NULL; 4-byte aligned */
 } CaFinal;
 
+/* Frames of cagpu_render / cagpu_render_maps (additive to v12): F pictures of height x width pixels, each of ONE env, drawn from the
+ * current state, the env's static map and a block of trajectory-tape rows by the drawing rules of DESIGN.md section 13.
+ * The window: pixel (row r, column c) has its centre at x = xmin + (16 c + 8) / s16, y = ymax - (16 r + 8) / s16,
+ * s16 = 16 x pixels per metre (row 0 is the top); a world coordinate becomes the 1/16-pixel integer
+ * floor((x - xmin) * s16) / floor((ymax - y) * s16), saturated at +-2^20, and every inside test is integer arithmetic.
+ * Frame f shows env frame_env[f] (outside [0, E): a white frame) and the history rows of slots first[f] .. last[f]
+ * (clamped to the block) of column frame_col[f] of `hist` (frame_col NULL: column frame_env[f]; a column outside the
+ * block: no agents) -- the rows of an agent are the slots whose column 11 is >= 0, in slot order.  last[f] < first[f]: a
+ * SNAPSHOT frame of the current state (one disc per agent that is not CA_ABSENT, its goal marker).  Several frames may
+ * show one env with growing `last`: the animation of an episode is one call. */
+typedef struct CaRender {
+  uint8_t *out;             /* device uint8 [F, height, width, 3] RGB, 16-byte aligned */
+  int32_t num_frames, height, width; /* F >= 1; height, width in [16, 1024] */
+  int32_t flags;            /* bit 0: circles_along_traj (visualize.py:175-228; clear: the scatter mode, :236-251);
+                               bit 1: draw the static map */
+  double xmin, ymax, s16;
+  const int32_t *frame_env; /* device int32 [F] */
+  const int32_t *frame_col; /* device int32 [F] or NULL */
+  const int32_t *first, *last; /* device int32 [F] */
+  const double *hist;       /* device [hist_steps, hist_cols, N, 12], rows as CaTraj.rows holds them, or NULL (no history:
+                               every frame with last >= first shows no agents); 16-byte aligned */
+  int32_t hist_steps, hist_cols;
+  int64_t stride_t, stride_s; /* doubles between two slots / two columns of `hist` (an agent's rows are 12 apart) */
+  void *work;               /* device scratch, 16-byte aligned: the frames' primitive lists */
+  uint64_t work_bytes;      /* >= cagpu_render_work_bytes(F, N, hist_steps) */
+} CaRender;
+
 /* GA3C-CADRL network weights (policies/GA3C_CADRL/checkpoints/<run>/network_*.data-00000-of-00001): device float
  * pointers in the checkpoint's own layout, kernels row-major [in, out].  LSTM gate order i, j, f, o. */
 typedef struct CaNet {
@@ -376,6 +403,27 @@ int cagpu_laserscan_maps(const CaParams *p, const CaState *s, const CaMapSet *se
  * (an index outside the set: empty static part, agents still drawn, bit 2 of the fault word). */
 int cagpu_occupancy_grid(const CaParams *p, const CaState *s, const CaMap *map, const CaOccGrid *grid, void *stream);
 int cagpu_occupancy_grid_maps(const CaParams *p, const CaState *s, const CaMapSet *set, const CaOccGrid *grid, void *stream);
+
+/* Replaces: visualize.plot_episode / draw_agents (envs/visualize.py:90-257; the per-episode PNG of
+ * collision_avoidance_env.py:240-270 and the frames animate_episode glues together) for r->num_frames frames at once,
+ * rasterised on the device (csrc/cagpu_render.inc): white background, the env's static grid (dark grey where a pixel centre
+ * falls in an occupied cell, Map.py:26-32), then per agent slot the discs along its trajectory (alpha 1 - t / (1.2 max_time)
+ * over white, one-pixel rim), the 3-pixel polylines, a goal diamond -- or dots and one disc without circles_along_traj.
+ * DIVERGENCES: no text, axes or anti-aliasing, a diamond for the goal star, the map is drawn (the reference has that line
+ * commented out, visualize.py:108-109).  Reads pos / goal / radius / flags of the state, the map and `hist`; writes r->out
+ * and r->work only: no simulator state, nothing to do at a reset, cagpu_last_kernel() is left alone.  Any num_agents up to
+ * 1024; primitives outside the window are clipped.  map may be NULL (or its static_bits): no map.  CA_EINVAL, nothing
+ * launched: NULL p / s / r or state pointers, bad sizes, out NULL or not 16-byte aligned, num_frames < 1, height / width
+ * outside [16, 1024], xmin / ymax not finite or s16 outside (0, 1e9], frame_env / first / last NULL, hist_steps < 0 or
+ * hist_steps > 0 with hist NULL / hist_cols < 1 / a negative stride, hist not 16-byte aligned, a bad CaMap, work NULL /
+ * misaligned / too small; the _maps form also: what cagpu_occupancy_grid_maps rejects of a set.  CA_EUNSUPPORTED: more
+ * than 2^31 - 1 records per frame or (frame, tile) workgroups.  The _maps form shows every env its OWN map env_map[e] (an
+ * index outside the set: no map, bit 2 of the fault word). */
+int cagpu_render(const CaParams *p, const CaState *s, const CaMap *map, const CaRender *r, void *stream);
+int cagpu_render_maps(const CaParams *p, const CaState *s, const CaMapSet *set, const CaRender *r, void *stream);
+/* Bytes of CaRender.work for F frames of N agent slots over a history block of hist_steps slots: 16 F + 32 F N (2 hist_steps + 2)
+ * (a 32-byte record per disc, dot, segment and marker; 0 for bad arguments).  Host-only call. */
+uint64_t cagpu_render_work_bytes(int32_t num_frames, int32_t num_agents, int32_t hist_steps);
 
 /* Replaces: GA3CCADRLPolicy.find_next_action (policies/GA3CCADRLPolicy.py:49-84) + NetworkVPCore.predict_p
  * (GA3C_CADRL/network.py:24-41, the TF1 graph of the checkpoint) for every agent whose policy is CA_POL_GA3C_CADRL and
