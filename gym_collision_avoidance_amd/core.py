@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from . import episodes
 
 _F64 = ("pos_x", "pos_y", "vel_x", "vel_y", "heading", "goal_x", "goal_y", "radius", "pref_speed",
         "time_remaining", "t", "slt", "ep_reward", "turning_dir")
@@ -151,6 +152,9 @@ class BatchedSim(object):
         # the final record (keep_final): the terminal observation / flag words of the envs an auto-reset overwrites
         self._fin_on, self._fin_obs, self._fin_flags = False, None, None
         self._cf = nat.CaFinal()
+        # the episode log (log_episodes): None = off; dict(rows [E, C, N, 4] f64, head [E, C, 4] i32, cursor [E] i64, cap)
+        self._log = None
+        self._cl = nat.CaEpLog()
 
     # ---------------------------------------------------------------- what the outside reads
     # `state` and the four outputs are those of the step last handed out: reading them goes through sync(), which rewinds a
@@ -446,6 +450,8 @@ class BatchedSim(object):
             self._ar, self._table = None, None
             if self._fin_on:        # (no auto-reset, nothing is overwritten: the final record goes with the table)
                 self.keep_final(False)
+            if self._log is not None:   # (... and no episode is ever logged)
+                self.log_episodes(on=False)
             return
         t = self._dev(table, torch.float64)
         assert t.dim() == 3 and t.shape[1:] == (self.N, 6), t.shape
@@ -483,6 +489,8 @@ class BatchedSim(object):
                                        None if h is None else h.data_ptr(), None if m is None else m.data_ptr(),
                                        self._stream()))
         self._keep = [c, h, m]  # keep alive until the stream has consumed them
+        if self._log is not None:   # the reset envs count their episodes from 0 again: undrained records of theirs are discarded
+            episodes.clear(self._log["head"], self._log["cursor"], m)
         if self._traj is not None:   # a host-side reset logs no row but ends the episode of the envs it touches (tape "epoch")
             tr = self._traj
             tr["epoch"] = tr["epoch"] + (1 if m is None else (m != 0).to(torch.int32))
@@ -657,7 +665,13 @@ class BatchedSim(object):
             fa = self._fast_args
             if fa is None:
                 ar = None if self._ar is None else C.byref(self._ar)
-                if self._fin_on:
+                if self._log is not None:
+                    fa = (self.lib.cagpu_step_log, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
+                                                    C.byref(self._map) if (self._map is not None and self._maps is None) else None,
+                                                    None if self._maps is None else C.byref(self._maps),
+                                                    C.byref(self._ct) if self._traj_on else None,
+                                                    C.byref(self._cf) if self._fin_on else None, C.byref(self._cl)))
+                elif self._fin_on:
                     fa = (self.lib.cagpu_step_final, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
                                                       C.byref(self._map) if (self._map is not None and self._maps is None) else None,
                                                       None if self._maps is None else C.byref(self._maps),
@@ -698,7 +712,15 @@ class BatchedSim(object):
             e = self.ga3c(None if e is None else self._ga3c_ext)
         if self.fresh_outputs:
             self._new_outputs()
-        if self._fin_on:
+        if self._log is not None:
+            nat.check(self.lib.cagpu_step_log(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
+                                              None if e is None else e.data_ptr(),
+                                              None if self._ar is None else C.byref(self._ar),
+                                              C.byref(self._map) if (self._map is not None and self._maps is None) else None,
+                                              None if self._maps is None else C.byref(self._maps),
+                                              C.byref(self._ct) if self._traj_on else None,
+                                              C.byref(self._cf) if self._fin_on else None, C.byref(self._cl), self._stream()))
+        elif self._fin_on:
             nat.check(self.lib.cagpu_step_final(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
                                                 None if e is None else e.data_ptr(),
                                                 None if self._ar is None else C.byref(self._ar),
@@ -742,7 +764,16 @@ class BatchedSim(object):
         e = self._dev(ext_actions, torch.float64)
         if self.fresh_outputs:
             self._new_outputs()
-        if self._fin_on:   # (one block: it ends up holding every env's most recent terminal record of the launch)
+        if self._log is not None:   # (every ending of the n steps goes to its own slot of the log; tape / final record as below)
+            chunk, ct = self._traj_chunk(int(n_steps)) if self._traj_on else (None, None)
+            nat.check(self.lib.cagpu_rollout_log(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
+                                                 None if e is None else e.data_ptr(),
+                                                 None if self._ar is None else C.byref(self._ar), int(n_steps), 0, 0,
+                                                 None if ct is None else C.byref(ct),
+                                                 C.byref(self._cf) if self._fin_on else None, C.byref(self._cl), self._stream()))
+            if chunk is not None:
+                self._traj_commit(chunk)
+        elif self._fin_on:   # (one block: it ends up holding every env's most recent terminal record of the launch)
             chunk, ct = self._traj_chunk(int(n_steps)) if self._traj_on else (None, None)
             nat.check(self.lib.cagpu_rollout_final(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
                                                    None if e is None else e.data_ptr(),
@@ -849,7 +880,16 @@ class BatchedSim(object):
         if not prep["in_kernel"]:
             la["snap"].copy_(self._slab)
         la["fin_ring"] = prep["fin_ring"]
-        if prep["fin_ring"] is not None:   # the ring's final blocks (slot t: the envs that auto-reset in step t), tape or not
+        if self._log is not None:   # the episode log (its records land in the envs' own rings, not in the output ring), with
+            chunk, ct = self._traj_chunk(k, prep.get("traj")) if rec else (None, None)   # the final blocks / the tape or without
+            rc = self.lib.cagpu_rollout_log(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, 1, prep["delta"],
+                                            None if ct is None else C.byref(ct), prep["cf_ref"], C.byref(self._cl),
+                                            _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
+            if rc != 0:
+                nat.check(rc)
+            if chunk is not None:
+                la["traj"] = self._traj_commit(chunk)
+        elif prep["fin_ring"] is not None:   # the ring's final blocks (slot t: the envs that auto-reset in step t), tape or not
             chunk, ct = self._traj_chunk(k, prep.get("traj")) if rec else (None, None)
             rc = self.lib.cagpu_rollout_final(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, 1, prep["delta"],
                                               None if ct is None else C.byref(ct), prep["cf_ref"],
@@ -1019,6 +1059,69 @@ class BatchedSim(object):
         if self._la is not None:
             self._la["prep"] = None   # (a prepared ring launch carries, or lacks, its final blocks)
             self._la["fin_ring"] = None
+
+    # ---------------------------------------------------------------- the episode log (include/cagpu.h CaEpLog)
+    def log_episodes(self, capacity=16, on=True):
+        """Log every finished episode on the device: when an env's episode ends and the env is auto-reset, the step kernel
+        itself (cagpu_step_log / cagpu_rollout_log, through step(), rollout() and step_lookahead() alike) stores the
+        reference's per-episode quantities (run_episode, experiments/src/env_utils.py:56-87) -- per agent total_reward,
+        time_to_goal, extra_time_to_goal and the final flag word; per episode its index, length, fixture case and outcome
+        -- in slot (episode index % capacity) of the env's own ring; episodes() drains what is new.  State, outputs and
+        statistics are bit-identical to a run without it.  `capacity` has to cover the episodes an env can finish between
+        two drains PLUS what a look-ahead ring computes ahead (at most one episode per ring step and env): older records
+        are overwritten and episodes() reports them as `dropped`.  16 + 32 N bytes per slot: 22 MB at 4096 x 10 and the
+        default capacity.  Needs a fixture table (set_fixture_table: without auto-reset no episode is logged); detaching the
+        table switches it off.  reset() discards the undrained records of the envs it resets (their episode count restarts
+        at 0).  Off by default: a sim that never calls this runs the calls and kernels it ran before."""
+        self.sync()
+        on = bool(on)
+        if on and self._ar is None:
+            raise nat.CagpuError("log_episodes: no fixture table attached (set_fixture_table): without auto-reset no episode "
+                                 "is ever logged -- read the state when `game_over` shows")
+        if on:
+            cap = int(capacity)
+            if cap < 1:
+                raise nat.CagpuError("log_episodes: capacity must be >= 1")
+            dev = self.device
+            head = torch.full((self.E, cap, 4), -1, dtype=torch.int32, device=dev)
+            rows = torch.zeros((self.E, cap, self.N, 4), dtype=torch.float64, device=dev)
+            # (a log switched on mid-run starts at the envs' current episode: earlier ones were never written)
+            cursor = self._state["reset_count"].to(torch.int64)
+            self._log = dict(rows=rows, head=head, cursor=cursor, cap=cap)
+            self._cl = nat.CaEpLog(rows=rows.data_ptr(), head=head.data_ptr(), capacity=cap)
+        else:
+            self._log = None
+            self._cl = nat.CaEpLog()
+        self._fast_args = None
+        if self._la is not None:
+            self._la["prep"] = None   # (a prepared ring launch is re-made: the next fill picks its entry point anew)
+
+    def _handed_out_reset_count(self):
+        """reset_count [E] at the step LAST HANDED OUT, without a rewind: mid-ring the state has run ahead, so it is the
+        count the ring started from (the snapshot slab) plus the game_over slots handed out since -- with a table attached
+        every game over is exactly one auto-reset"""
+        la = self._la
+        if la is None or la["slots"] is None or la["t"] >= la["len"]:
+            return self._state["reset_count"]
+        off = self._state["reset_count"].data_ptr() - self._slab.data_ptr()
+        rc = la["snap"][off:off + 4 * self.E].view(torch.int32).to(torch.int64)
+        if la["t"] > 0:
+            rc = rc + la["ring"][3][:la["t"]].sum(0, dtype=torch.int64)
+        return rc
+
+    def episodes(self):
+        """Drain the episode log -> dict of device tensors with the M episodes finished since the last drain, ordered by
+        (env, episode): `env`, `episode` (the env's k-th episode since its last reset()), `case` (row of the fixture table it
+        ran on), `steps`, `outcome` (0 collision / 1 all at goal / 2 stuck) [M] int64; `total_reward`, `time_to_goal`,
+        `extra_time_to_goal` [M, N] float64; `flags` [M, N] int32 (nat.decode_flags) -- and `dropped`, a Python int: the
+        episodes that ended since the last drain but whose records were overwritten first (capacity too small).  Episodes
+        of steps a look-ahead ring has computed but not handed out yet stay in the log for a later drain; the call neither
+        rewinds nor drops the ring.  Synchronises with the device (M is read back)."""
+        if self._log is None:
+            raise nat.CagpuError("episodes: the episode log is off (log_episodes)")
+        lg = self._log
+        out, lg["cursor"] = episodes.drain(lg["rows"], lg["head"], lg["cursor"], self._handed_out_reset_count())
+        return out
 
     # ---------------------------------------------------------------- the trajectory tape (include/cagpu.h CaTraj)
     TRAJ_BLOCK_BYTES = 8 << 20   # step(): slots are taken from blocks of about this size (at most 64 slots), not a tensor per step

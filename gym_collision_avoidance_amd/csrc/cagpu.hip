@@ -93,7 +93,34 @@ struct KArgs {
   // The blocks advance with the output ring (ring_obs / ring_agent: 0 unless every step keeps its outputs).
   float* fin_obs;
   uint32_t* fin_flags;
+  // episode log (cagpu_step_log / cagpu_rollout_log; nullptr everywhere else): CaEpLog.rows [E, C, N, 4] / CaEpLog.head
+  // [E, C, 4] and the capacity C.  The blocks never advance: a record's slot is a function of (env, episode index) alone.
+  double* log_rows;
+  int32_t* log_head;
+  int32_t log_cap;
+  int32_t log_case_step;  // case_stride mod n_cases in [0, n_cases): the case an episode ran on from the next one's, no division
 };
+
+// One agent's share of an episode-log record (CaEpLog): env e ends its episode number `ep` (its reset count before the
+// increment) and every agent lane stores its 32-byte row of slot ep % C of the env's own ring as two 16-byte stores;
+// agent 0's lane stores the 16-byte head {ep, steps, case, outcome} as well.  Plain stores, no ordering between envs.
+// `next_case` is the table row the auto-reset is about to load, (env_id_offset + e + (ep + 1) case_stride) mod n_cases: the
+// ended episode ran on the row case_step = case_stride mod n_cases before it.
+__device__ __forceinline__ void eplog_store(double* const rows, int32_t* const head, const int cap, const long e,
+                                            const int next_case, const int case_step, const int n_cases, const int N,
+                                            const int a, const int ep, const double ep_reward, const double t,
+                                            const double extra, const uint32_t flags, const int steps, const bool any_coll,
+                                            const bool all_goal) {
+  const long slot = e * cap + ep % cap;
+  double2* q = reinterpret_cast<double2*>(rows + (slot * N + a) * 4);
+  q[0] = make_double2(ep_reward, t);
+  q[1] = make_double2(extra, __longlong_as_double(static_cast<long long>(flags)));  // (low 32 bits: the word; high 32: zero)
+  if (a == 0) {
+    int c = next_case - case_step;
+    if (c < 0) c += n_cases;
+    *reinterpret_cast<int4*>(head + slot * 4) = make_int4(ep, steps, c, any_coll ? 0 : (all_goal ? 1 : 2));
+  }
+}
 
 // One row of the trajectory tape (CaTraj): the reference's global_state_history row (agent.py:275-287) + its index.
 // 96 bytes = six 16-byte stores; the rows of a tile's lanes are contiguous.
@@ -1572,6 +1599,10 @@ LP1_UNROLL
                                                    static_cast<unsigned>(reset_cnt), static_cast<unsigned>(a));
             }
             if (k.fin_flags) k.fin_flags[i + ring_a] = r.flags;  // final record (CaFinal): the terminal step's flag word
+            // episode log (CaEpLog): the three addends of this lane, its flag word and -- agent 0 -- the episode's head
+            if (k.log_rows)
+              eplog_store(k.log_rows, k.log_head, k.log_cap, e, static_cast<int>(c), k.log_case_step, k.n_cases, N, a,
+                          reset_cnt - 1, sh_r0[lane], sh_r1[lane], sh_r2[lane], r.flags, ep_step, any_coll, all_goal);
             reset_lane(r, k.table + (c * N + a) * 6, k.heading_seed != 0, h0, p);
             // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by its agent 0 lane
             if (!MULTI && k.map_seed && a == 0) k.env_map[e] = map_draw(k.map_seed, k.env_id_offset + e, reset_cnt, k.num_maps);
@@ -2016,8 +2047,10 @@ int launch_pipe2(const KArgs& k0, hipStream_t st) {
   std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_pipe_kernel<%d, %d, %s> grid=%u lds=%zu mode=%d%s%s%s", NC, TE,
                 MULTI ? "true" : "false", grid, static_cast<size_t>(G::LDS), k.mode, k.yield_t > 0 ? " fair" : "",
                 k.traj_rows ? " traj" : "", k.fin_obs ? " final" : "");
-  // (recording and the final record are template flags: the instantiations without them are the code they were before)
-  if (k.fin_obs) {
+  if (k.log_rows) std::strncat(g_last_kernel, " log", sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
+  // (recording and the final record are template flags: the instantiations without them are the code they were before;
+  // the episode log rides on the FINAL instantiations behind a uniform test of its pointers -- no flag of its own)
+  if (k.fin_obs || k.log_rows) {
     const bool fair = MULTI && k.yield_t > 0;
     if (k.traj_rows) {
       if (fair) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, MULTI, true, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
@@ -2223,7 +2256,14 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
                      int32_t n_steps, void* stream, const CaMap* map = nullptr, const bool ring = false,
                      const int64_t snapshot_delta = 0, const bool query_snapshot = false, const CaMapSet* set = nullptr,
                      const CaTraj* traj = nullptr, const bool want_traj = false, const CaFinal* fin = nullptr,
-                     const bool want_fin = false) {
+                     const bool want_fin = false, const CaEpLog* log = nullptr, const bool want_log = false) {
+  if (want_log) {  // (first, like the final record's: a bad episode log is reported as such whatever else is wrong)
+    if (!log || !log->rows || !log->head) return fail(CA_EINVAL, "cagpu: NULL CaEpLog, CaEpLog.rows or CaEpLog.head%s");
+    if ((reinterpret_cast<uintptr_t>(log->rows) & 15u) || (reinterpret_cast<uintptr_t>(log->head) & 15u))
+      return fail(CA_EINVAL, "cagpu: CaEpLog.rows and CaEpLog.head must be 16-byte aligned%s");
+    if (log->capacity < 1) return fail(CA_EINVAL, "cagpu: CaEpLog.capacity must be >= 1%s");
+    if (!ar) return fail(CA_EINVAL, "cagpu: a CaEpLog without a CaAutoReset (no auto-reset, no episode is ever logged)%s");
+  }
   if (want_fin) {  // (first, like the tape's: a bad final record is reported as such whatever else is wrong with the call)
     if (!fin || !fin->obs) return fail(CA_EINVAL, "cagpu: NULL CaFinal or CaFinal.obs%s");
     if ((reinterpret_cast<uintptr_t>(fin->obs) & 15u) || (reinterpret_cast<uintptr_t>(fin->flags) & 3u))
@@ -2266,6 +2306,10 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
   k.n_steps = n_steps; k.mode = MODE_STEP;
   if (want_traj) { k.traj_rows = traj->rows; k.traj_ep = traj->episode; }
   if (want_fin) { k.fin_obs = fin->obs; k.fin_flags = fin->flags; }
+  if (want_log) {
+    k.log_rows = log->rows; k.log_head = log->head; k.log_cap = log->capacity;
+    k.log_case_step = static_cast<int32_t>(((k.case_stride % k.n_cases) + k.n_cases) % k.n_cases);
+  }
   k.inv_rvo_dt = 1.0 / p->rvo_dt;
   {
     static std::atomic<int> seq{0};
@@ -2333,6 +2377,22 @@ int cagpu_rollout_final(const CaParams* p, const CaState* s, const CaOut* o, con
   if (!ring && snapshot_delta != 0) return fail(CA_EINVAL, "cagpu_rollout_final: snapshot_delta without ring%s");
   return step_impl(p, s, o, ext_actions, ar, n_steps, stream, nullptr, ring != 0, snapshot_delta, false, nullptr, traj,
                    traj != nullptr, fin, true);
+}
+
+int cagpu_step_log(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
+                   const CaMap* map, const CaMapSet* set, const CaTraj* traj, const CaFinal* fin, const CaEpLog* log,
+                   void* stream) {
+  if (map && set) return fail(CA_EINVAL, "cagpu_step_log: a CaMap and a CaMapSet at once%s");
+  return step_impl(p, s, o, ext_actions, ar, 1, stream, map, false, 0, false, set, traj, traj != nullptr, fin, fin != nullptr,
+                   log, true);
+}
+
+int cagpu_rollout_log(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
+                      int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj* traj, const CaFinal* fin,
+                      const CaEpLog* log, void* stream) {
+  if (!ring && snapshot_delta != 0) return fail(CA_EINVAL, "cagpu_rollout_log: snapshot_delta without ring%s");
+  return step_impl(p, s, o, ext_actions, ar, n_steps, stream, nullptr, ring != 0, snapshot_delta, false, nullptr, traj,
+                   traj != nullptr, fin, fin != nullptr, log, true);
 }
 
 static int laserscan_impl(const CaParams* p, const CaState* s, const CaMap* map, const CaScan* scan, void* stream,

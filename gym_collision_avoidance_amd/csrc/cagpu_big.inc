@@ -400,6 +400,10 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
           for (int q = 0; q < W; ++q) dst[q] = src[q];
           if (k.fin_flags) k.fin_flags[i] = r.flags;
         }
+        // episode log (CaEpLog): this thread's three addends and flag word, and -- agent 0 -- the episode's head
+        if (k.log_rows)
+          eplog_store(k.log_rows, k.log_head, k.log_cap, e, static_cast<int>(c), k.log_case_step, k.n_cases, N, a,
+                      reset_cnt - 1, sh_r0[a], sh_r1[a], sh_r2[a], r.flags, ep_step, any_coll, all_goal);
         reset_lane(r, k.table + (c * N + a) * 6, k.heading_seed != 0, h0, p);
         statics_dirty = true;
         do_sense = true;

@@ -862,6 +862,11 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
             const long c = (k.env_id_offset + env0 + le + static_cast<long>(reset_cnt) * k.case_stride) % k.n_cases;
             // final record (CaFinal): the flag word as the terminal step leaves it, in the slot of this step's outputs
             if (FINAL && k.fin_flags) (k.fin_flags + out_base)[lane] = flags;
+            // episode log (CaEpLog; a uniform test inside the FINAL instantiations): this lane's three addends and flag
+            // word, and -- agent 0 -- the episode's head, in slot (episode index % capacity) of the env's own ring
+            if (FINAL && k.log_rows)
+              eplog_store(k.log_rows, k.log_head, k.log_cap, env0 + le, static_cast<int>(c), k.log_case_step, k.n_cases, N, a,
+                          reset_cnt - 1, sh_epr[lane], sh_t[lane], sh_r2[lane], flags, ep_step, any_coll, all_goal);
             Lane r;
             r.flags = flags;
             reset_lane(r, k.table + (c * N + a) * 6, false, 0.0, p);
@@ -1175,10 +1180,11 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
           // final record (CaFinal): the terminal rows are complete in the output block by now (the fences above: P4 of the
           // three waves, A3 of wave 0) -- every lane saves the elements it is about to overwrite, in the block that advances
           // with the output ring
-          float* fin = FINAL ? k.fin_obs + (dst - k.o.obs) : nullptr;
+          // (k.fin_obs == nullptr inside a FINAL instantiation: the episode log alone is on)
+          float* fin = (FINAL && k.fin_obs) ? k.fin_obs + (dst - k.o.obs) : nullptr;
           for (int q = ts; q < N * W; q += S_PAIR) {
             const int a2 = q / W, col = q - a2 * W;
-            if (FINAL) fin[q] = dst[q];
+            if (FINAL && fin) fin[q] = dst[q];
             float v = src[q];
             if (col == 0)  // (is_learning comes from the live flags; the row of an absent slot is all zeros: radius 0)
               v = ((sh_flag[le2 * N + a2] & CA_IS_LEARNING) && !(ragged && !(src[q + 5] > 0.f))) ? 1.f : 0.f;

@@ -139,6 +139,7 @@ class CollisionAvoidanceEnv(Env):
         self._host_dynamics, self._hostdyn_by_env, self._ext_state = [], None, None
         self._traj_req = None     # record_trajectories(): dict(max_bytes) while recording is asked for
         self._final_req = False   # keep_final_observations()
+        self._log_req = None      # log_episodes(): the capacity asked for (None: default) while the log is asked for
 
     # ------------------------------------------------------------------ configuration (reference setters)
     def set_agents(self, agents):
@@ -149,7 +150,7 @@ class CollisionAvoidanceEnv(Env):
 
     def set_fixture_suite(self, num_agents, policies="RVO", agents_dynamics="unicycle", auto_reset=True,
                           env_id_offset=0, case_stride=None, table=None, generate=None, random_headings=None,
-                          heading_seed=1, agents_sensors=("other_agents_states",)):
+                          heading_seed=1, agents_sensors=("other_agents_states",), agent_setup=None):
         """Batched evaluation on the reference's 500-case suite (run_full_test_suite.py:54-130): env e starts on case
         (env_id_offset + e) % 500 and, with auto_reset, its k-th episode loads case (env_id_offset + e + k*stride) % 500
         on the device (DummyVecEnv semantics, vec_env.py:120-128).
@@ -165,7 +166,10 @@ class CollisionAvoidanceEnv(Env):
         headings -- at reset() and at every on-device auto-reset -- are uniform in [-pi, pi) instead of pointing at the
         goal; drawn on the device from `heading_seed`.
         `agents_sensors`: the sensor names (test_cases.sensor_dict) of every agent, e.g. ("other_agents_states",
-        "laserscan", "occupancy_grid") under Config.USE_STATIC_MAP."""
+        "laserscan", "occupancy_grid") under Config.USE_STATIC_MAP.
+        `agent_setup`: callable(agent), run by reset() on each Agent object it builds for the batch's slots -- what the
+        reference's reset_env does after full_test_suite (policy.initialize_network(**spec), sensor.set_args(...),
+        run_full_test_suite.py:70-80); every env of the batch runs what those agents describe."""
         if generate is not None:
             assert table is None and int(generate["num_cases"]) >= 1 and "seed" in generate
             table = None
@@ -177,7 +181,7 @@ class CollisionAvoidanceEnv(Env):
             assert table.ndim == 3 and tuple(table.shape[1:]) == (num_agents, 6), table.shape
         self._fixture = dict(table=table, policies=policies, dynamics=agents_dynamics, auto_reset=auto_reset,
                              env_id_offset=env_id_offset, num_agents=num_agents, generate=generate,
-                             sensors=tuple(agents_sensors),
+                             sensors=tuple(agents_sensors), agent_setup=agent_setup,
                              heading_seed=(int(heading_seed) or 1) if (random_headings if random_headings is not None
                                                                       else not Config.EVALUATE_MODE) else 0,
                              case_stride=self.num_envs if case_stride is None else case_stride)
@@ -316,6 +320,9 @@ class CollisionAvoidanceEnv(Env):
             row0 = row0[row0[:, 5] > 0]   # (a ragged table pads short cases with radius-0 rows: empty slots)
             self.agents = tc.cadrl_test_case_to_agents(row0, policies=f["policies"], agents_dynamics=f["dynamics"],
                                                        agents_sensors=f["sensors"])
+            if f.get("agent_setup") is not None:
+                for a in self.agents:
+                    f["agent_setup"](a)
         else:
             if self.default_agents is None:
                 if E > 1:
@@ -439,6 +446,9 @@ class CollisionAvoidanceEnv(Env):
             f = self._fixture
             slots = agents0 if len(agents0) == N else tc.cadrl_test_case_to_agents(
                 np.ones((N, 6)), policies=f["policies"], agents_dynamics=f["dynamics"])   # (plugin ids of EVERY slot)
+            if slots is not agents0 and f.get("agent_setup") is not None:
+                for a in slots:
+                    f["agent_setup"](a)
             pol, dyn, isl, stl = self._plugin_ids(slots)
             if slots is not agents0:
                 self._plugin_ids(agents0)  # leaves self._host_policies describing env 0
@@ -448,6 +458,10 @@ class CollisionAvoidanceEnv(Env):
             if self._final_req:    # (asked for before reset(), or the batch was rebuilt)
                 self._check_final()
                 sim.keep_final(True)
+            if self._log_req is not None:    # (asked for before reset(), or the batch was rebuilt)
+                self._check_log()
+                if sim._log is None:
+                    sim.log_episodes(capacity=self._log_capacity())
             idx = (np.arange(E) + f["env_id_offset"]) % len(f["table"])
             if hasattr(f["table"], "data_ptr"):
                 import torch
@@ -468,6 +482,8 @@ class CollisionAvoidanceEnv(Env):
         else:
             if self._final_req:
                 self._check_final()
+            if self._log_req is not None:
+                self._check_log()
             sim.set_fixture_table(None)
             groups = [g if g is not None else agents0 for g in per_env]
             ids, self._host_by_env, self._hostdyn_by_env = [], [], []
@@ -950,6 +966,57 @@ class CollisionAvoidanceEnv(Env):
         if self._fixture is not None and not self._fixture["auto_reset"]:
             raise ValueError("keep_final_observations() with auto_reset=False: no env is ever reset on the device, the "
                              "terminal observation is the one step() returns")
+
+    # ------------------------------------------------------------------ the episode log (core.BatchedSim.log_episodes)
+    LOG_CAPACITY = 16
+
+    def log_episodes(self, on=True, capacity=None):
+        """Batched mode with on-device auto-reset (set_fixture_suite(..., auto_reset=True)): log every finished episode
+        on the device -- the step kernels store run_episode's per-episode statistics (env_utils.py:56-87) at the
+        auto-reset that ends the episode, whether the steps come from step(), rollout() or the look-ahead ring --;
+        episode_log() returns the episodes finished since it was last called.  `capacity`: episodes the log holds per env
+        (default 16): enough for what an env finishes between two episode_log() calls plus what the look-ahead ring
+        computes ahead (at most one episode per ring step); what does not fit is reported as `dropped`.  Off (the
+        default): step() / rollout() run the kernels they ran before; they return exactly what they did either way.  May
+        be called before or after reset() and survives reset() (which discards undrained episodes)."""
+        if not on:
+            self._log_req = None
+            if self._sim is not None and self._sim._log is not None:
+                self._sim.log_episodes(on=False)
+            return
+        self._log_req = {"capacity": None if capacity is None else int(capacity)}
+        self._check_log()
+        if self._sim is not None:
+            self._sim.log_episodes(capacity=self._log_capacity())
+
+    def _log_capacity(self):
+        cap = self._log_req["capacity"]
+        if cap is not None:
+            return cap
+        return self.LOG_CAPACITY
+
+    def _check_log(self):
+        if self.num_envs <= 1:
+            raise ValueError("log_episodes() is for batched envs (num_envs > 1)")
+        if self._fixture is None and (self.default_agents is not None or self._sim is not None):
+            raise ValueError("log_episodes() needs the on-device auto-reset of set_fixture_suite(..., auto_reset=True): "
+                             "without it no episode ends on the device")
+        if self._fixture is not None and not self._fixture["auto_reset"]:
+            raise ValueError("log_episodes() with auto_reset=False: no env is ever reset on the device, read the state "
+                             "when game_over shows")
+
+    def episode_log(self):
+        """The episodes finished since the last call (or since log_episodes()), ordered by (env, episode) -> dict of numpy
+        arrays in the row schema of experiments.run_full_test_suite.run_suite: `env`, `episode`, `test_case`, `num_agents`
+        (slots that hold an agent), `steps` [M]; `total_reward`, `time_to_goal`, `extra_time_to_goal` [M, N] (0 in empty
+        slots); `total_time_to_goal`, `collision`, `all_at_goal`, `any_stuck`, `outcome` ("collision" / "all_at_goal" /
+        "stuck") [M] -- and `dropped`, the number of episodes that ended but were overwritten before this call (int).
+        `env` is this shard's env index (add env_id_offset for the global one).  Does not rewind the look-ahead ring."""
+        if self._sim is None or self._sim._log is None:
+            raise RuntimeError("episode_log(): the episode log is off (log_episodes(), then reset())")
+        from gym_collision_avoidance_amd import episodes as eplog
+        ep = self._sim.episodes()
+        return eplog.suite_columns({k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in ep.items()})
 
     def _resize_ring(self):
         """the default ring length follows the bytes of a slot (see _upload): recomputed when the final record is toggled"""

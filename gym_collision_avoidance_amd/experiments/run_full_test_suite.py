@@ -74,6 +74,63 @@ def run_suite(policy="RVO", num_agents=4, test_cases=None, device="cuda:0", max_
     return pd.DataFrame(rows)
 
 
+def run_suite_logged(policy="RVO", num_agents=4, test_cases=None, num_envs=None, device="cuda:0", chunk=256, max_steps=200000):
+    """run_suite() through the on-device episode log (CollisionAvoidanceEnv.log_episodes): `num_envs` envs (default
+    min(number of cases, 64)) walk the table of `test_cases` with the on-device auto-reset -- env e runs cases e,
+    e + num_envs, ... --, env.rollout() advances the batch `chunk` steps per call (one fused launch where every policy is
+    answered inside the step kernel) and the log is drained after every chunk until every case has its first record.
+    No env per case, no per-step latching on the host.  -> the same DataFrame as run_suite, one row per case, in case order
+    (bit for bit where a case is the first episode of its env; later episodes start from the device's own arctan2)."""
+    import pandas as pd
+    spec = policies[policy]
+    cases = list(range(len(tc.fixture_table(num_agents)))) if test_cases is None else list(test_cases)
+    E = min(len(cases), 64) if num_envs is None else int(num_envs)
+    if E < 2:
+        raise ValueError("run_suite_logged needs a batch (num_envs > 1): use run_suite for a single case")
+
+    def setup(agent):   # what the reference's reset_env does after full_test_suite (run_full_test_suite.py:70-80)
+        if "checkpt_name" in spec:
+            agent.policy.initialize_network(**spec)
+        for s in agent.sensors:
+            if "sensor_args" in spec:
+                s.set_args(spec["sensor_args"])
+
+    env = CollisionAvoidanceEnv(num_envs=E, device=device)
+    env.set_fixture_suite(num_agents, policies=spec["policy"], auto_reset=True, case_stride=E,
+                          table=tc.fixture_table(num_agents)[cases],
+                          agents_sensors=tuple(spec.get("sensors", ["other_agents_states"])), agent_setup=setup)
+    # an env finishes at most one episode per step: a capacity of `chunk` can never overflow between two drains
+    env.log_episodes(capacity=int(chunk))
+    env.reset()
+    if Config.EVALUATE_MODE:
+        # run_suite's initial state, bit for bit: the reference gives every agent the heading numpy's arctan2 computes
+        # (test_cases.py:554-556, one scalar call per agent); the fixture batch computes it on the device, whose libm may
+        # differ from it in the last bit.  (Episodes that start at an on-device auto-reset use the device's.)
+        sub = tc.fixture_table(num_agents)[cases]
+        start = sub[np.arange(E) % len(sub)]
+        heads = np.array([[np.arctan2(float(r[3]) - float(r[1]), float(r[2]) - float(r[0])) for r in g] for g in start])
+        env._sim.reset(start, headings=heads)
+    first, steps = {}, 0
+    while len(first) < len(cases) and steps < max_steps:
+        env.rollout(int(chunk))
+        steps += int(chunk)
+        log = env.episode_log()
+        assert log["dropped"] == 0, log["dropped"]
+        for i, c in enumerate(log["test_case"]):    # (a case several envs ran: the record with the lowest episode index)
+            if int(c) not in first or int(log["episode"][i]) < int(first[int(c)]["episode"]):
+                first[int(c)] = {k: v[i] for k, v in log.items() if k != "dropped"}
+    rows = []
+    for j, c in enumerate(cases):
+        r = first[j]     # (cases the batch never finished within max_steps raise here)
+        ttg = np.array(r["time_to_goal"])
+        rows.append({"num_agents": num_agents, "policy": policy, "test_case": c,
+                     "total_reward": np.array(r["total_reward"]), "steps": int(r["steps"]),
+                     "time_to_goal": ttg, "total_time_to_goal": float(ttg.sum()),
+                     "extra_time_to_goal": np.array(r["extra_time_to_goal"]), "collision": bool(r["collision"]),
+                     "all_at_goal": bool(r["all_at_goal"]), "any_stuck": bool(r["any_stuck"]), "outcome": str(r["outcome"])})
+    return pd.DataFrame(rows)
+
+
 def main():
     import pandas as pd
     frames = []

@@ -283,6 +283,30 @@ typedef struct CaFinal {
   uint32_t *flags;  /* device [E, N] (ring: [n_steps, E, N]) or NULL; 4-byte aligned */
 } CaFinal;
 
+/* Episode log of cagpu_step_log / cagpu_rollout_log: one record per FINISHED EPISODE, written by the step kernels at the
+ * auto-reset that would otherwise overwrite it -- the per-episode quantities of the reference's run_episode
+ * (experiments/src/env_utils.py:56-87), which CaState.env_stats keeps only as sums.  Every env owns a ring of `capacity`
+ * slots; when env e ends its k-th episode (k = CaState.reset_count[e] BEFORE the increment) and is auto-reset in the same
+ * step, the record goes to slot k % capacity of env e's ring: a pure function of (e, k) -- no atomic, no shared counter, no
+ * order between envs -- so one launch per step, cagpu_rollout, a look-ahead ring and a rewind-and-replay all write the same
+ * bytes to the same place.  Slots of envs that end no episode are LEFT ALONE; the caller initialises `head` to -1 and
+ * recognises a valid slot by its stamp head[..., 0] == k.  An older record is overwritten once the env is `capacity`
+ * episodes further. */
+typedef struct CaEpLog {
+  double  *rows;   /* device [E, C, N, 4], 16-byte aligned.  Per agent slot:
+                      0 total_reward (CaState.ep_reward), 1 time_to_goal (t), 2 extra_time_to_goal (t - slt)
+                        -- 0..2 are exactly the three per-agent addends that the kernel sums into env_stats[e][5..7];
+                      3: the agent's flag word as the terminal step leaves it (what CaFinal.flags holds),
+                         bit pattern in the low 32 bits of the 8 bytes, high 32 bits zero */
+  int32_t *head;   /* device [E, C, 4], 16-byte aligned: {k, steps, case, outcome}
+                      k       = reset_count[e] BEFORE the increment (index of the env's episode that just ended)
+                      steps   = the value added to env_stats[e][4]
+                      case    = row of CaAutoReset.table the ended episode ran on:
+                                (env_id_offset + e + k * case_stride) % n_cases
+                      outcome = 0 collision / 1 all at goal / 2 stuck (the env_stats[1..3] classification) */
+  int32_t capacity, reserved0;   /* C >= 1 */
+} CaEpLog;
+
 /* Frames of cagpu_render / cagpu_render_maps (additive to v12): F pictures of height x width pixels, each of ONE env, drawn from the
  * current state, the env's static map and a block of trajectory-tape rows by the drawing rules of DESIGN.md section 13.
  * The window: pixel (row r, column c) has its centre at x = xmin + (16 c + 8) / s16, y = ymax - (16 r + 8) / s16,
@@ -535,6 +559,22 @@ int cagpu_step_final(const CaParams *p, const CaState *s, const CaOut *o, const 
 int cagpu_rollout_final(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                         int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj *traj, const CaFinal *fin,
                         void *stream);
+
+/* The step / rollout calls that also write the EPISODE LOG (CaEpLog): supersets of cagpu_step_final / cagpu_rollout_final
+ * -- `traj` and `fin` may each be NULL, `log` may not --, the same kernel selection, grid and block; state, outputs,
+ * statistics (and the tape, and the final record) are bit-identical to the calls they mirror.  Every kernel that auto-resets
+ * writes it, with ordinary stores from the lanes that hold the values: the pipelined kernels through their " final"
+ * instantiations (a uniform test of the log pointers inside; cagpu_last_kernel() shows " log" behind the name), the general
+ * and the large-env kernel behind a uniform test.  A ring launch logs the episodes of steps that are not handed out yet; a
+ * replay from a rewind point rewrites the same records bit for bit.  CA_EINVAL, nothing launched: log, log->rows or
+ * log->head NULL, either not 16-byte aligned, capacity < 1, log without ar (no episode is ever logged then), both map and
+ * set given, snapshot_delta without ring -- plus whatever the mirrored call rejects. */
+int cagpu_step_log(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
+                   const CaMap *map, const CaMapSet *set, const CaTraj *traj, const CaFinal *fin, const CaEpLog *log,
+                   void *stream);
+int cagpu_rollout_log(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
+                      int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj *traj, const CaFinal *fin,
+                      const CaEpLog *log, void *stream);
 
 /* The policy query of the NEXT step ahead of time (collision_avoidance_env.py:305-323 for the built-in RVO policy):
  * fills s->next_action from the CURRENT state and sets CA_PLAN_VALID, without stepping.  cagpu_step / cagpu_rollout keep
