@@ -85,6 +85,13 @@ class CaEpLog(C.Structure):
     _fields_ = [("rows", _P), ("head", _P), ("capacity", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class CaStepEx(C.Structure):
+    """one step / rollout launch (cagpu_step_ex).  The five record pointers are plain addresses (C.addressof of a CaMap /
+    CaMapSet / CaTraj / CaFinal / CaEpLog, None = not used): whoever stores one keeps that struct alive"""
+    _fields_ = [("n_steps", C.c_int32), ("ring", C.c_int32), ("snapshot_delta", C.c_int64), ("map", _P), ("set", _P),
+                ("traj", _P), ("fin", _P), ("log", _P)]
+
+
 class CaRender(C.Structure):
     _fields_ = [("out", _P), ("num_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("flags", C.c_int32),
                 ("xmin", C.c_double), ("ymax", C.c_double), ("s16", C.c_double), ("frame_env", _P), ("frame_col", _P),
@@ -108,7 +115,7 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_ga3c_packed_bytes", "cagpu_ga3c_pack", "cagpu_rollout_ring", "cagpu_ring_snapshots", "cagpu_debug_copy8", "cagpu_device_faults_async",
            "cagpu_step_maps", "cagpu_laserscan_maps", "cagpu_occupancy_grid", "cagpu_occupancy_grid_maps",
            "cagpu_step_traj", "cagpu_rollout_traj", "cagpu_step_final", "cagpu_rollout_final",
-           "cagpu_step_log", "cagpu_rollout_log",
+           "cagpu_step_log", "cagpu_rollout_log", "cagpu_step_ex",
            "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes")
 
 _lib = None
@@ -156,6 +163,7 @@ def lib():
                                  C.POINTER(CaFinal), C.POINTER(CaEpLog), _P]
     L.cagpu_rollout_log.argtypes = [PP, PS, PO, _P, PA, C.c_int32, C.c_int32, C.c_int64, C.POINTER(CaTraj),
                                     C.POINTER(CaFinal), C.POINTER(CaEpLog), _P]
+    L.cagpu_step_ex.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaStepEx), _P]
     L.cagpu_render.argtypes = [PP, PS, C.POINTER(CaMap), C.POINTER(CaRender), _P]
     L.cagpu_render_maps.argtypes = [PP, PS, C.POINTER(CaMapSet), C.POINTER(CaRender), _P]
     L.cagpu_render_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

@@ -6,6 +6,7 @@ Reference objects this replaces: the list[Agent] owned by CollisionAvoidanceEnv 
 agent.py:29-138) and the per-step loops of collision_avoidance_env.py:156-234.
 """
 import ctypes as C
+import functools
 import math
 import os
 
@@ -54,8 +55,7 @@ GA3C_DEFAULT_WEIGHTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 
                                     "network_01900000.npz")
 
 
-# the current stream's raw handle without building a torch.cuda.Stream object around it (1.2 -> 0.3 us on the way to a launch)
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # (see BatchedSim._stream_handle)
 
 
 class BatchedSim(object):
@@ -105,7 +105,6 @@ class BatchedSim(object):
         self._variants = []       # per-agent sensor arguments beyond the primary pair (set_sensor_variants)
         if not self.pipeline:
             self._cs.next_action = None
-        self._p_ref, self._cs_ref = C.byref(self.p), C.byref(self._cs)   # (cached: the structs live as long as the sim)
         self._co = nat.CaOut(obs=self._obs.data_ptr(), rewards=self._rewards.data_ptr(), done=self._done.data_ptr(),
                              game_over=self._game_over.data_ptr(),
                              actions=self.actions.data_ptr() if record_actions else None,
@@ -122,7 +121,18 @@ class BatchedSim(object):
         # (tests/test_gpu_parity.py::test_step_rewrites_every_output_element), so nothing is carried over in them.
         self.fresh_outputs = False
         self._ar = None
-        self._fast_args = None    # prebuilt ctypes arguments of the external-action-free step (see step())
+        # Every step / rollout launch is ONE call, cagpu_step_ex, and what varies between launches is data: self._sx is the
+        # CaStepEx of a single step, whose map / set / traj / fin / log addresses are set where the feature is switched
+        # (set_map, _traj_switch, keep_final, log_episodes) and point at structs this object holds and rewrites IN PLACE.
+        # The references below are made once: p, _cs, _co and _sx are never replaced; _ar is, by set_fixture_table only,
+        # which re-makes _ar_ref.
+        self._step_ex = self.lib.cagpu_step_ex
+        self._sx = nat.CaStepEx(n_steps=1)
+        self._p_ref, self._cs_ref, self._co_ref, self._sx_ref = C.byref(self.p), C.byref(self._cs), C.byref(self._co), C.byref(self._sx)
+        self._ar_ref = None
+        # the current stream's raw handle (no torch.cuda.Stream object is built around it: 1.2 -> 0.3 us on the way to a launch)
+        self._stream_handle = (functools.partial(_raw_stream, self._dev_index) if _raw_stream else
+                               lambda: torch.cuda.current_stream(self.device).cuda_stream)
         self._table = None
         self._keep = []
         self._map = None
@@ -180,7 +190,7 @@ class BatchedSim(object):
 
     # ---------------------------------------------------------------- plumbing
     def _stream(self):
-        return C.c_void_p(_raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
+        return C.c_void_p(self._stream_handle())
 
     def _dev(self, x, dtype):
         if x is None:
@@ -203,7 +213,6 @@ class BatchedSim(object):
             if not hasattr(self.p, k_):
                 raise AttributeError("CaParams has no field %r" % k_)
             setattr(self.p, k_, v)
-        self._fast_args = None
         if self._la is not None:
             self._la["in_kernel"].clear()
             self._la["prep"] = None
@@ -225,7 +234,6 @@ class BatchedSim(object):
         Both None: switched off (the deterministic kernels, pipelined plan included).  The reference draws from numpy's
         global stream, one agent after the other: the batched draws are the same distributions, not the same numbers."""
         self.sync()
-        self._fast_args = None
         # (whichever branch is not configured below must not keep pointing at a tensor of an earlier configuration)
         self._cs.rvo_collab = None
         self._cs.rvo_heading_noise = None
@@ -442,12 +450,11 @@ class BatchedSim(object):
         heading_seed != 0: training mode (test_cases.py:558-559) -- an auto-reset draws the initial heading uniformly in
         [-pi, pi) on the device (Philox of seed, global env id, reset count, agent) instead of pointing at the goal."""
         self.sync()
-        self._fast_args = None
         if self._la is not None:
             self._la["in_kernel"].clear()
             self._la["prep"] = None
         if table is None:
-            self._ar, self._table = None, None
+            self._ar, self._ar_ref, self._table = None, None, None
             if self._fin_on:        # (no auto-reset, nothing is overwritten: the final record goes with the table)
                 self.keep_final(False)
             if self._log is not None:   # (... and no episode is ever logged)
@@ -474,6 +481,7 @@ class BatchedSim(object):
                                    reset_obs=self._reset_obs.data_ptr(),
                                    reset_plan=None if self._reset_plan is None else self._reset_plan.data_ptr(),
                                    heading_seed=int(heading_seed) & 0xFFFFFFFFFFFFFFFF)
+        self._ar_ref = C.byref(self._ar)
 
     # ---------------------------------------------------------------- the C-ABI calls
     def reset(self, cases, headings=None, mask=None):
@@ -516,14 +524,14 @@ class BatchedSim(object):
 
         A MAP SET (include/cagpu.h CaMapSet): `static_map` a bool stack [M, rows, cols] -- every env has its own map,
         the device int32 tensor `env_map` [E] (default: env e on map e % M; an explicit one must hold indices in
-        [0, M)), and step() / laserscan() run the cagpu_step_maps / cagpu_laserscan_maps entry points.  map_seed != 0:
+        [0, M)), and step() / laserscan() hand the kernels the CaMapSet (CaStepEx.set / cagpu_laserscan_maps).  map_seed != 0:
         every auto-reset of an env draws its next map on the device (the reference draws a map per episode,
         collision_avoidance_env.py:274-275, :384-385) with a key that every explicit reset() draws anew from a generator
         seeded by map_seed (`map_seed` property: the key in force); 0: every env keeps its map."""
         self.sync()
         bits = None
-        self._fast_args = None
         self._maps, self._map_rng, self.env_map = None, None, None
+        self._sx.map, self._sx.set = None, None   # (re-pointed below, once the new structs exist)
         self.occ, self.occ_bits, self._occ = None, None, None   # (sized by the map's cell: set_occupancy_grid() again)
         M = 0
         if static_map is not None:
@@ -547,6 +555,11 @@ class BatchedSim(object):
             if int(map_seed):
                 self._map_rng = np.random.Generator(np.random.PCG64(int(map_seed) & 0xFFFFFFFFFFFFFFFF))
                 self._maps.map_seed = int(map_seed) & 0xFFFFFFFFFFFFFFFF
+        # a single step takes the set, or else the one map (set_map_seed / set_env_map rewrite the CaMapSet / its tensor in place)
+        if M:
+            self._sx.set = C.addressof(self._maps)
+        else:
+            self._sx.map = C.addressof(self._map)
         R = len(np.arange(0, max_range, range_res))
         self.scan_hist = torch.full((self.E, self.N, num_to_store, num_beams), 255, dtype=torch.uint8,
                                     device=self.device)
@@ -659,98 +672,35 @@ class BatchedSim(object):
             if self._ext_state is not None:
                 assert tuple(self._ext_state.shape) == (self.E, self.N, 5), self._ext_state.shape
             self._cs.ext_state = None if self._ext_state is None else self._ext_state.data_ptr()
-        if ext_actions is None and not self._has_ga3c:
-            # env.step(None) with built-in policies only (env_utils.py:50): the per-step host path is one ctypes call
-            # with prebuilt arguments -- at ~20 us per launch the interpreter is otherwise on the critical path
-            fa = self._fast_args
-            if fa is None:
-                ar = None if self._ar is None else C.byref(self._ar)
-                if self._log is not None:
-                    fa = (self.lib.cagpu_step_log, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
-                                                    C.byref(self._map) if (self._map is not None and self._maps is None) else None,
-                                                    None if self._maps is None else C.byref(self._maps),
-                                                    C.byref(self._ct) if self._traj_on else None,
-                                                    C.byref(self._cf) if self._fin_on else None, C.byref(self._cl)))
-                elif self._fin_on:
-                    fa = (self.lib.cagpu_step_final, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
-                                                      C.byref(self._map) if (self._map is not None and self._maps is None) else None,
-                                                      None if self._maps is None else C.byref(self._maps),
-                                                      C.byref(self._ct) if self._traj_on else None, C.byref(self._cf)))
-                elif self._traj_on:
-                    fa = (self.lib.cagpu_step_traj, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
-                                                     C.byref(self._map) if (self._map is not None and self._maps is None) else None,
-                                                     None if self._maps is None else C.byref(self._maps), C.byref(self._ct)))
-                elif self._maps is not None:
-                    fa = (self.lib.cagpu_step_maps, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
-                                                     C.byref(self._maps)))
-                elif self._map is not None:
-                    fa = (self.lib.cagpu_step_map, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar,
-                                                    C.byref(self._map)))
-                else:
-                    fa = (self.lib.cagpu_step, (C.byref(self.p), C.byref(self._cs), C.byref(self._co), None, ar))
-                self._fast_args = fa
-            if self.fresh_outputs:
-                self._new_outputs()
-            rc = fa[0](*fa[1], _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                nat.check(rc)
+        # env.step(None) with built-in policies only (env_utils.py:50): the per-step host path is the one ctypes call below
+        # with references made once -- at ~20 us per launch the interpreter is otherwise on the critical path
+        fast = ext_actions is None and not self._has_ga3c
+        e = ext = None
+        if not fast:
+            e = self._dev(ext_actions, torch.float64)
+            if e is not None:
+                assert tuple(e.shape) == (self.E, self.N, 2), e.shape
+            if self._has_ga3c:  # policy query on the pre-step observation (collision_avoidance_env.py:319-323)
+                if e is not None:  # the caller's external actions travel in the same buffer; never write into theirs
+                    if self._ga3c_ext is None:
+                        self._ga3c_ext = torch.zeros((self.E, self.N, 2), dtype=torch.float64, device=self.device)
+                    self._ga3c_ext.copy_(e)
+                e = self.ga3c(None if e is None else self._ga3c_ext)
+            ext = None if e is None else e.data_ptr()
+        if self.fresh_outputs:
+            self._new_outputs()
+        rc = self._step_ex(self._p_ref, self._cs_ref, self._co_ref, ext, self._ar_ref, self._sx_ref, self._stream_handle())
+        if rc != 0:
+            nat.check(rc)
+        if fast:
             self._steps_since_probe += 1
             if self._steps_since_probe >= 256:
                 self._steps_since_probe = 0
                 self._fault_probe()
-            if self._variants:
-                self._apply_sensor_variants()
-            return self._obs, self._rewards, self._game_over
-        e = self._dev(ext_actions, torch.float64)
-        if e is not None:
-            assert tuple(e.shape) == (self.E, self.N, 2), e.shape
-        if self._has_ga3c:  # policy query on the pre-step observation (collision_avoidance_env.py:319-323)
-            if e is not None:  # the caller's external actions travel in the same buffer; never write into theirs
-                if self._ga3c_ext is None:
-                    self._ga3c_ext = torch.zeros((self.E, self.N, 2), dtype=torch.float64, device=self.device)
-                self._ga3c_ext.copy_(e)
-            e = self.ga3c(None if e is None else self._ga3c_ext)
-        if self.fresh_outputs:
-            self._new_outputs()
-        if self._log is not None:
-            nat.check(self.lib.cagpu_step_log(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                              None if e is None else e.data_ptr(),
-                                              None if self._ar is None else C.byref(self._ar),
-                                              C.byref(self._map) if (self._map is not None and self._maps is None) else None,
-                                              None if self._maps is None else C.byref(self._maps),
-                                              C.byref(self._ct) if self._traj_on else None,
-                                              C.byref(self._cf) if self._fin_on else None, C.byref(self._cl), self._stream()))
-        elif self._fin_on:
-            nat.check(self.lib.cagpu_step_final(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                                None if e is None else e.data_ptr(),
-                                                None if self._ar is None else C.byref(self._ar),
-                                                C.byref(self._map) if (self._map is not None and self._maps is None) else None,
-                                                None if self._maps is None else C.byref(self._maps),
-                                                C.byref(self._ct) if self._traj_on else None, C.byref(self._cf),
-                                                self._stream()))
-        elif self._traj_on:
-            nat.check(self.lib.cagpu_step_traj(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                               None if e is None else e.data_ptr(),
-                                               None if self._ar is None else C.byref(self._ar),
-                                               C.byref(self._map) if (self._map is not None and self._maps is None) else None,
-                                               None if self._maps is None else C.byref(self._maps), C.byref(self._ct),
-                                               self._stream()))
-        elif self._maps is not None:
-            nat.check(self.lib.cagpu_step_maps(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                               None if e is None else e.data_ptr(),
-                                               None if self._ar is None else C.byref(self._ar), C.byref(self._maps),
-                                               self._stream()))
-        elif self._map is not None:
-            nat.check(self.lib.cagpu_step_map(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                              None if e is None else e.data_ptr(),
-                                              None if self._ar is None else C.byref(self._ar), C.byref(self._map),
-                                              self._stream()))
         else:
-            nat.check(self.lib.cagpu_step(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                          None if e is None else e.data_ptr(),
-                                          None if self._ar is None else C.byref(self._ar), self._stream()))
-        self._keep = [e]
-        self._apply_sensor_variants()
+            self._keep = [e]
+        if self._variants:
+            self._apply_sensor_variants()
         return self._obs, self._rewards, self._game_over
 
     def rollout(self, n_steps, ext_actions=None):
@@ -764,35 +714,14 @@ class BatchedSim(object):
         e = self._dev(ext_actions, torch.float64)
         if self.fresh_outputs:
             self._new_outputs()
-        if self._log is not None:   # (every ending of the n steps goes to its own slot of the log; tape / final record as below)
-            chunk, ct = self._traj_chunk(int(n_steps)) if self._traj_on else (None, None)
-            nat.check(self.lib.cagpu_rollout_log(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                                 None if e is None else e.data_ptr(),
-                                                 None if self._ar is None else C.byref(self._ar), int(n_steps), 0, 0,
-                                                 None if ct is None else C.byref(ct),
-                                                 C.byref(self._cf) if self._fin_on else None, C.byref(self._cl), self._stream()))
-            if chunk is not None:
-                self._traj_commit(chunk)
-        elif self._fin_on:   # (one block: it ends up holding every env's most recent terminal record of the launch)
-            chunk, ct = self._traj_chunk(int(n_steps)) if self._traj_on else (None, None)
-            nat.check(self.lib.cagpu_rollout_final(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                                   None if e is None else e.data_ptr(),
-                                                   None if self._ar is None else C.byref(self._ar), int(n_steps), 0, 0,
-                                                   None if ct is None else C.byref(ct), C.byref(self._cf), self._stream()))
-            if chunk is not None:
-                self._traj_commit(chunk)
-        elif self._traj_on:
-            chunk, ct = self._traj_chunk(int(n_steps))
-            nat.check(self.lib.cagpu_rollout_traj(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                                  None if e is None else e.data_ptr(),
-                                                  None if self._ar is None else C.byref(self._ar), int(n_steps), 0, 0,
-                                                  C.byref(ct), self._stream()))
+        # the n steps' CaStepEx: no map (as ever), the tape's own chunk, the single-step final block -- it ends up holding every
+        # env's most recent terminal record of the launch -- and the log, every ending in its own slot
+        chunk, ct = self._traj_chunk(int(n_steps)) if self._traj_on else (None, None)
+        sx = nat.CaStepEx(n_steps=int(n_steps), traj=None if ct is None else C.addressof(ct), fin=self._sx.fin, log=self._sx.log)
+        nat.check(self._step_ex(self._p_ref, self._cs_ref, self._co_ref, None if e is None else e.data_ptr(), self._ar_ref,
+                                C.byref(sx), self._stream_handle()))
+        if chunk is not None:
             self._traj_commit(chunk)
-        else:
-            nat.check(self.lib.cagpu_rollout(C.byref(self.p), C.byref(self._cs), C.byref(self._co),
-                                             None if e is None else e.data_ptr(),
-                                             None if self._ar is None else C.byref(self._ar), int(n_steps),
-                                             self._stream()))
         self._keep = [e]
         self._apply_sensor_variants()
         return self._obs, self._rewards, self._game_over
@@ -824,7 +753,7 @@ class BatchedSim(object):
         return not (self._has_ga3c or self._rvo is not None or self._variants or self._map is not None)
 
     def enable_lookahead(self, k, fresh=True, adaptive=False, start=None):
-        """Serve step(None) from a ring of `k` steps computed ahead of time in ONE launch (cagpu_rollout_ring): with every
+        """Serve step(None) from a ring of `k` steps computed ahead of time in ONE launch (CaStepEx.ring): with every
         policy internal a step needs nothing from the host (env_utils.py:45-52 passes None until the episode is over),
         so step_lookahead() hands out slot t of the ring and launches the next k steps when it runs dry -- the fused
         n-step kernel never waits for the slowest workgroup of a step (7.7 instead of 14.9 us per step at 4096 x 10).
@@ -880,36 +809,17 @@ class BatchedSim(object):
         if not prep["in_kernel"]:
             la["snap"].copy_(self._slab)
         la["fin_ring"] = prep["fin_ring"]
-        if self._log is not None:   # the episode log (its records land in the envs' own rings, not in the output ring), with
-            chunk, ct = self._traj_chunk(k, prep.get("traj")) if rec else (None, None)   # the final blocks / the tape or without
-            rc = self.lib.cagpu_rollout_log(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, 1, prep["delta"],
-                                            None if ct is None else C.byref(ct), prep["cf_ref"], C.byref(self._cl),
-                                            _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                nat.check(rc)
-            if chunk is not None:
-                la["traj"] = self._traj_commit(chunk)
-        elif prep["fin_ring"] is not None:   # the ring's final blocks (slot t: the envs that auto-reset in step t), tape or not
-            chunk, ct = self._traj_chunk(k, prep.get("traj")) if rec else (None, None)
-            rc = self.lib.cagpu_rollout_final(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, 1, prep["delta"],
-                                              None if ct is None else C.byref(ct), prep["cf_ref"],
-                                              _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                nat.check(rc)
-            if chunk is not None:
-                la["traj"] = self._traj_commit(chunk)
-        elif rec:             # the ring's own chunk of the tape: slot t of the launch records step t
-            chunk, ct = self._traj_chunk(k, prep.get("traj"))
-            rc = self.lib.cagpu_rollout_traj(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, 1, prep["delta"], C.byref(ct),
-                                             _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                nat.check(rc)
+        # the launch's CaStepEx was prepared with the ring (final blocks, the episode log -- its records land in the envs' own
+        # rings, not in the output ring); the ring's own chunk of the tape is taken now: slot t of the launch records step t
+        chunk = None
+        if rec:
+            chunk, ct = self._traj_chunk(k, prep["traj"])
+            prep["sx"].traj = C.addressof(ct)
+        rc = self._step_ex(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], prep["sx_ref"], self._stream_handle())
+        if rc != 0:
+            nat.check(rc)
+        if chunk is not None:
             la["traj"] = self._traj_commit(chunk)
-        else:
-            rc = self.lib.cagpu_rollout_ring(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], k, prep["delta"],
-                                             _raw_stream(self._dev_index) if _raw_stream else torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                nat.check(rc)
         la["slots"] = prep["slots"]
         la["co_live"] = prep["co"]      # (keeps the ctypes struct the launch was given alive)
         la["t"], la["len"] = 0, k
@@ -943,7 +853,7 @@ class BatchedSim(object):
         co = nat.CaOut.from_buffer_copy(self._co)   # (the ring's own CaOut: the workspace of self._co, no actions / orca_vel record)
         co.actions, co.orca_vel = None, None
         co.obs, co.rewards, co.done, co.game_over = obs.data_ptr(), rew.data_ptr(), done.data_ptr(), over.data_ptr()
-        ar_ref = None if self._ar is None else C.byref(self._ar)
+        ar_ref = self._ar_ref
         # the rewind point = the state BEFORE the k steps: stored by the pipelined n-step kernel itself as it loads its
         # tiles (snapshot_delta: the snapshot slab has the state slab's layout); by one device copy in front of the launch
         # for the other kernels
@@ -956,10 +866,11 @@ class BatchedSim(object):
             in_kernel = la["in_kernel"][key] = rc == 1
         # (the kernels write 0 / 1 bytes: reinterpreted as bool without a conversion kernel)
         slots = list(zip(obs.unbind(0), rew.unbind(0), done.view(torch.bool).unbind(0), over.view(torch.bool).unbind(0)))
+        sx = nat.CaStepEx(n_steps=k, ring=1, snapshot_delta=(la["snap"].data_ptr() - self._slab.data_ptr()) if in_kernel else 0,
+                          fin=None if cf is None else C.addressof(cf), log=self._sx.log)
         return dict(k=k, key=key, ring=ring, co=co, co_ref=C.byref(co), ar_ref=ar_ref, in_kernel=in_kernel, slots=slots,
-                    fin_ring=fin_ring, cf=cf, cf_ref=None if cf is None else C.byref(cf),
-                    traj=self._traj_alloc(k) if self._traj_on else None,   # (always its own tensors, fresh ring or not)
-                    delta=(la["snap"].data_ptr() - self._slab.data_ptr()) if in_kernel else 0)
+                    fin_ring=fin_ring, cf=cf, sx=sx, sx_ref=C.byref(sx),   # (cf: kept alive for sx.fin)
+                    traj=self._traj_alloc(k) if self._traj_on else None)   # (always its own tensors, fresh ring or not)
 
     def step_lookahead(self):
         """one step(None) served from the look-ahead ring -> (obs [E,N,W], rewards [E,N], done [E,N] bool, game_over [E] bool)"""
@@ -1017,8 +928,8 @@ class BatchedSim(object):
         if t < k:
             self._slab.copy_(la["snap"])
             if t > 0:              # (rewrites slot t - 1 with the values it already holds)
-                nat.check(self.lib.cagpu_rollout(C.byref(self.p), C.byref(self._cs), C.byref(self._co), None,
-                                                 None if self._ar is None else C.byref(self._ar), t, self._stream()))
+                nat.check(self._step_ex(self._p_ref, self._cs_ref, self._co_ref, None, self._ar_ref,
+                                        C.byref(nat.CaStepEx(n_steps=t)), self._stream_handle()))
 
     # ---------------------------------------------------------------- the final record (include/cagpu.h CaFinal)
     @property
@@ -1030,7 +941,7 @@ class BatchedSim(object):
         """Keep, for every env that auto-resets in a step, what the reset overwrites: the observation rows of the terminal
         step (`final_obs`, float32 [E, N, W] -- the vector-env APIs' final_observation / terminal_observation) and the
         agents' flag words as that step left them (`final_flags`, int32 [E, N] bit patterns: nat.decode_flags names the
-        endings).  Stored by the step kernels themselves (cagpu_step_final / cagpu_rollout_final) through step(),
+        endings).  Stored by the step kernels themselves (CaStepEx.fin of cagpu_step_ex) through step(),
         rollout() and step_lookahead() alike; state, outputs and statistics are bit-identical to a run without it.  Rows
         are valid where `game_over` is set and UNSPECIFIED elsewhere.  After rollout(n) the record holds every env's most
         recent ending of those n steps (valid for the last step where `game_over` is set).  Needs a fixture table
@@ -1055,7 +966,7 @@ class BatchedSim(object):
         if not on:
             self._fin_obs, self._fin_flags = None, None
             self._cf.obs, self._cf.flags = None, None
-        self._fast_args = None
+        self._sx.fin = C.addressof(self._cf) if on else None
         if self._la is not None:
             self._la["prep"] = None   # (a prepared ring launch carries, or lacks, its final blocks)
             self._la["fin_ring"] = None
@@ -1063,7 +974,7 @@ class BatchedSim(object):
     # ---------------------------------------------------------------- the episode log (include/cagpu.h CaEpLog)
     def log_episodes(self, capacity=16, on=True):
         """Log every finished episode on the device: when an env's episode ends and the env is auto-reset, the step kernel
-        itself (cagpu_step_log / cagpu_rollout_log, through step(), rollout() and step_lookahead() alike) stores the
+        itself (CaStepEx.log of cagpu_step_ex, through step(), rollout() and step_lookahead() alike) stores the
         reference's per-episode quantities (run_episode, experiments/src/env_utils.py:56-87) -- per agent total_reward,
         time_to_goal, extra_time_to_goal and the final flag word; per episode its index, length, fixture case and outcome
         -- in slot (episode index % capacity) of the env's own ring; episodes() drains what is new.  State, outputs and
@@ -1088,13 +999,13 @@ class BatchedSim(object):
             # (a log switched on mid-run starts at the envs' current episode: earlier ones were never written)
             cursor = self._state["reset_count"].to(torch.int64)
             self._log = dict(rows=rows, head=head, cursor=cursor, cap=cap)
-            self._cl = nat.CaEpLog(rows=rows.data_ptr(), head=head.data_ptr(), capacity=cap)
+            self._cl.rows, self._cl.head, self._cl.capacity = rows.data_ptr(), head.data_ptr(), cap   # (in place: _sx.log)
         else:
             self._log = None
-            self._cl = nat.CaEpLog()
-        self._fast_args = None
+            self._cl.rows, self._cl.head, self._cl.capacity = None, None, 0
+        self._sx.log = C.addressof(self._cl) if on else None
         if self._la is not None:
-            self._la["prep"] = None   # (a prepared ring launch is re-made: the next fill picks its entry point anew)
+            self._la["prep"] = None   # (a prepared ring launch is re-made: its CaStepEx carries, or lacks, the log)
 
     def _handed_out_reset_count(self):
         """reset_count [E] at the step LAST HANDED OUT, without a rewind: mid-ring the state has run ahead, so it is the
@@ -1134,7 +1045,7 @@ class BatchedSim(object):
     def record_trajectories(self, max_bytes=1 << 30):
         """Record every agent's trajectory on the device from the next step on: the step kernels themselves write the
         reference's Agent.global_state_history row (agent.py:257-289) of every agent that moves, through step(),
-        rollout() and step_lookahead() alike (cagpu_step_traj / cagpu_rollout_traj).  Off by default -- the reference's
+        rollout() and step_lookahead() alike (CaStepEx.traj of cagpu_step_ex).  Off by default -- the reference's
         Config.STORE_HISTORY default does not switch it on for a batch (96 bytes per agent and step).  max_bytes: the
         budget of the tape; the launch that would take it past the budget raises CagpuError BEFORE it runs (nothing is
         dropped silently, the tape stays valid; clear_trajectories() makes room); a look-ahead ring is shortened to what
@@ -1160,7 +1071,7 @@ class BatchedSim(object):
 
     def _traj_switch(self, on):
         self._traj_on = bool(on)
-        self._fast_args = None
+        self._sx.traj = C.addressof(self._ct) if self._traj_on else None   # (_traj_slot rewrites _ct in place)
         if self._traj is not None:
             self._traj["open"] = None
         if self._la is not None:

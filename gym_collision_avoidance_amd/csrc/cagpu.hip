@@ -2252,11 +2252,35 @@ static int check_map_set(const CaMapSet* set, const char* who) {
   return CA_OK;
 }
 
+// One step / rollout call as step_impl sees it: the CaStepEx fields plus what only the fixed entry points need.
+struct StepCall {
+  int32_t n_steps = 1;
+  bool ring = false;
+  int64_t snapshot_delta = 0;
+  const CaMap* map = nullptr;
+  const CaMapSet* set = nullptr;
+  const CaTraj* traj = nullptr;
+  const CaFinal* fin = nullptr;
+  const CaEpLog* log = nullptr;
+  // the record the entry point insists on (the older names: "traj may not be NULL" ...); cagpu_step_ex: none
+  enum Need { NEED_NONE, NEED_SET, NEED_TRAJ, NEED_FIN, NEED_LOG } need = NEED_NONE;
+  bool query_snapshot = false;   // cagpu_ring_snapshots: answer 1 / 0 instead of launching
+  const char* who = "cagpu";     // the entry point's name in the messages that carry one
+};
+
 static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const double* ext, const CaAutoReset* ar,
-                     int32_t n_steps, void* stream, const CaMap* map = nullptr, const bool ring = false,
-                     const int64_t snapshot_delta = 0, const bool query_snapshot = false, const CaMapSet* set = nullptr,
-                     const CaTraj* traj = nullptr, const bool want_traj = false, const CaFinal* fin = nullptr,
-                     const bool want_fin = false, const CaEpLog* log = nullptr, const bool want_log = false) {
+                     const StepCall& c, void* stream) {
+  const CaMapSet* set = c.set;
+  const CaTraj* traj = c.traj;
+  const CaFinal* fin = c.fin;
+  const CaEpLog* log = c.log;
+  const int32_t n_steps = c.n_steps;
+  const bool want_log = log || c.need == StepCall::NEED_LOG;
+  const bool want_fin = fin || c.need == StepCall::NEED_FIN;
+  const bool want_traj = traj || c.need == StepCall::NEED_TRAJ;
+  if (c.need == StepCall::NEED_SET && !set) return fail(CA_EINVAL, "%s: NULL CaMapSet", c.who);
+  if (c.map && set) return fail(CA_EINVAL, "%s: a CaMap and a CaMapSet at once", c.who);
+  if (!c.ring && c.snapshot_delta != 0) return fail(CA_EINVAL, "%s: snapshot_delta without ring", c.who);
   if (want_log) {  // (first, like the final record's: a bad episode log is reported as such whatever else is wrong)
     if (!log || !log->rows || !log->head) return fail(CA_EINVAL, "cagpu: NULL CaEpLog, CaEpLog.rows or CaEpLog.head%s");
     if ((reinterpret_cast<uintptr_t>(log->rows) & 15u) || (reinterpret_cast<uintptr_t>(log->head) & 15u))
@@ -2279,7 +2303,9 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
   if (rc) return rc;
   if (set && (rc = check_map_set(set, "cagpu_step_maps"))) return rc;
   if (n_steps < 1) return fail(CA_EINVAL, "cagpu: n_steps must be >= 1%s");
-  if ((n_steps > 1 || ring) && (s->rvo_collab || s->rvo_heading_noise || s->ext_state))
+  if ((c.map || set) && (n_steps > 1 || c.ring))   // (only cagpu_step_ex can ask for it: the n-step kernels take no map)
+    return fail(CA_EINVAL, "%s: a CaMap / CaMapSet with n_steps > 1 or ring (single steps only)", c.who);
+  if ((n_steps > 1 || c.ring) && (s->rvo_collab || s->rvo_heading_noise || s->ext_state))
     return fail(CA_EINVAL, "cagpu: CaState.rvo_collab / rvo_heading_noise / ext_state are inputs of ONE step (the caller draws / "
                            "integrates them per step): not accepted by a multi-step call%s");
   KArgs k;
@@ -2292,9 +2318,9 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
     k.reset_obs = ar->heading_seed ? nullptr : ar->reset_obs;  // (a reset observation depends on the heading)
     k.reset_plan = ar->heading_seed ? nullptr : ar->reset_plan;
   }
-  if (map && map->static_bits) {
-    if (map->rows < 1 || map->cols < 1 || !(map->cell > 0.0)) return fail(CA_EINVAL, "cagpu: bad CaMap%s");
-    k.map = *map;
+  if (c.map && c.map->static_bits) {
+    if (c.map->rows < 1 || c.map->cols < 1 || !(c.map->cell > 0.0)) return fail(CA_EINVAL, "cagpu: bad CaMap%s");
+    k.map = *c.map;
   }
   if (set) {  // (single step: the n-step kernels take no set)
     k.map = set->map;
@@ -2315,7 +2341,7 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
     static std::atomic<int> seq{0};
     k.launch_seq = seq.fetch_add(1, std::memory_order_relaxed) + 1;
   }
-  if (ring) {
+  if (c.ring) {
     k.ring_agent = static_cast<int64_t>(p->num_envs) * p->num_agents;
     k.ring_obs = k.ring_agent * (6 + 7 * p->max_obs);
     k.ring_env = p->num_envs;
@@ -2326,10 +2352,10 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
 #else
     const bool can = n_steps > 1 && pipe_eligible(k);
 #endif
-    if (query_snapshot) return can ? 1 : 0;
-    if (snapshot_delta != 0 && !can)
+    if (c.query_snapshot) return can ? 1 : 0;
+    if (c.snapshot_delta != 0 && !can)
       return fail(CA_EUNSUPPORTED, "cagpu_rollout_ring: snapshot_delta needs the pipelined n-step kernel (cagpu_ring_snapshots() == 1 for these arguments)%s");
-    k.snap_delta = snapshot_delta;
+    k.snap_delta = c.snapshot_delta;
   }
 #ifdef CAGPU_ABLATE
   if (const char* ab = std::getenv("CAGPU_ABLATE")) k.ablate = std::atoi(ab);
@@ -2337,62 +2363,85 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
   return launch_any(k, stream);
 }
 
+int cagpu_step_ex(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
+                  const CaStepEx* x, void* stream) {
+  StepCall c;
+  c.who = "cagpu_step_ex";
+  if (x) {
+    c.n_steps = x->n_steps; c.ring = x->ring != 0; c.snapshot_delta = x->snapshot_delta;
+    c.map = x->map; c.set = x->set; c.traj = x->traj; c.fin = x->fin; c.log = x->log;
+  }
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
+}
+
+// The eleven fixed entry points: each is the CaStepEx its arguments spell, plus the record it insists on.
 int cagpu_step(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                void* stream) {
-  return step_impl(p, s, o, ext_actions, ar, 1, stream);
+  StepCall c;
+  c.who = "cagpu_step";
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 int cagpu_step_map(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                    const CaMap* map, void* stream) {
-  return step_impl(p, s, o, ext_actions, ar, 1, stream, map);
+  StepCall c;
+  c.who = "cagpu_step_map"; c.map = map;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 int cagpu_step_maps(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                     const CaMapSet* set, void* stream) {
-  if (!set) return fail(CA_EINVAL, "cagpu_step_maps: NULL CaMapSet%s");
-  return step_impl(p, s, o, ext_actions, ar, 1, stream, nullptr, false, 0, false, set);
+  StepCall c;
+  c.who = "cagpu_step_maps"; c.set = set; c.need = StepCall::NEED_SET;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 int cagpu_step_traj(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                     const CaMap* map, const CaMapSet* set, const CaTraj* traj, void* stream) {
-  if (map && set) return fail(CA_EINVAL, "cagpu_step_traj: a CaMap and a CaMapSet at once%s");
-  return step_impl(p, s, o, ext_actions, ar, 1, stream, map, false, 0, false, set, traj, true);
+  StepCall c;
+  c.who = "cagpu_step_traj"; c.map = map; c.set = set; c.traj = traj; c.need = StepCall::NEED_TRAJ;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 int cagpu_rollout_traj(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                        int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj* traj, void* stream) {
-  if (!ring && snapshot_delta != 0) return fail(CA_EINVAL, "cagpu_rollout_traj: snapshot_delta without ring%s");
-  return step_impl(p, s, o, ext_actions, ar, n_steps, stream, nullptr, ring != 0, snapshot_delta, false, nullptr, traj, true);
+  StepCall c;
+  c.who = "cagpu_rollout_traj"; c.n_steps = n_steps; c.ring = ring != 0; c.snapshot_delta = snapshot_delta;
+  c.traj = traj; c.need = StepCall::NEED_TRAJ;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 int cagpu_step_final(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                      const CaMap* map, const CaMapSet* set, const CaTraj* traj, const CaFinal* fin, void* stream) {
-  if (map && set) return fail(CA_EINVAL, "cagpu_step_final: a CaMap and a CaMapSet at once%s");
-  return step_impl(p, s, o, ext_actions, ar, 1, stream, map, false, 0, false, set, traj, traj != nullptr, fin, true);
+  StepCall c;
+  c.who = "cagpu_step_final"; c.map = map; c.set = set; c.traj = traj; c.fin = fin; c.need = StepCall::NEED_FIN;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 int cagpu_rollout_final(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                         int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj* traj, const CaFinal* fin,
                         void* stream) {
-  if (!ring && snapshot_delta != 0) return fail(CA_EINVAL, "cagpu_rollout_final: snapshot_delta without ring%s");
-  return step_impl(p, s, o, ext_actions, ar, n_steps, stream, nullptr, ring != 0, snapshot_delta, false, nullptr, traj,
-                   traj != nullptr, fin, true);
+  StepCall c;
+  c.who = "cagpu_rollout_final"; c.n_steps = n_steps; c.ring = ring != 0; c.snapshot_delta = snapshot_delta;
+  c.traj = traj; c.fin = fin; c.need = StepCall::NEED_FIN;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 int cagpu_step_log(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                    const CaMap* map, const CaMapSet* set, const CaTraj* traj, const CaFinal* fin, const CaEpLog* log,
                    void* stream) {
-  if (map && set) return fail(CA_EINVAL, "cagpu_step_log: a CaMap and a CaMapSet at once%s");
-  return step_impl(p, s, o, ext_actions, ar, 1, stream, map, false, 0, false, set, traj, traj != nullptr, fin, fin != nullptr,
-                   log, true);
+  StepCall c;
+  c.who = "cagpu_step_log"; c.map = map; c.set = set; c.traj = traj; c.fin = fin; c.log = log; c.need = StepCall::NEED_LOG;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 int cagpu_rollout_log(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                       int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj* traj, const CaFinal* fin,
                       const CaEpLog* log, void* stream) {
-  if (!ring && snapshot_delta != 0) return fail(CA_EINVAL, "cagpu_rollout_log: snapshot_delta without ring%s");
-  return step_impl(p, s, o, ext_actions, ar, n_steps, stream, nullptr, ring != 0, snapshot_delta, false, nullptr, traj,
-                   traj != nullptr, fin, fin != nullptr, log, true);
+  StepCall c;
+  c.who = "cagpu_rollout_log"; c.n_steps = n_steps; c.ring = ring != 0; c.snapshot_delta = snapshot_delta;
+  c.traj = traj; c.fin = fin; c.log = log; c.need = StepCall::NEED_LOG;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 static int laserscan_impl(const CaParams* p, const CaState* s, const CaMap* map, const CaScan* scan, void* stream,
@@ -2669,16 +2718,22 @@ int cagpu_generate_cases_ragged(int64_t num_cases, int32_t max_agents, int32_t n
 
 int cagpu_rollout(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                   int32_t n_steps, void* stream) {
-  return step_impl(p, s, o, ext_actions, ar, n_steps, stream);
+  StepCall c;
+  c.who = "cagpu_rollout"; c.n_steps = n_steps;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 int cagpu_rollout_ring(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
                        int32_t n_steps, int64_t snapshot_delta, void* stream) {
-  return step_impl(p, s, o, ext_actions, ar, n_steps, stream, nullptr, true, snapshot_delta);
+  StepCall c;
+  c.who = "cagpu_rollout_ring"; c.n_steps = n_steps; c.ring = true; c.snapshot_delta = snapshot_delta;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
 int cagpu_ring_snapshots(const CaParams* p, const CaState* s, const CaOut* o, const CaAutoReset* ar, int32_t n_steps) {
-  return step_impl(p, s, o, nullptr, ar, n_steps, nullptr, nullptr, true, 0, true);
+  StepCall c;
+  c.who = "cagpu_ring_snapshots"; c.n_steps = n_steps; c.ring = true; c.query_snapshot = true;
+  return step_impl(p, s, o, nullptr, ar, c, nullptr);
 }
 
 int cagpu_plan(const CaParams* p, const CaState* s, void* stream) {

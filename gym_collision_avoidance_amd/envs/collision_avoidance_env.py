@@ -69,7 +69,7 @@ class CollisionAvoidanceEnv(Env):
 
         lookahead (batched mode only): `step(None)` of a batch whose policies are all internal needs nothing from the
         host (the reference's run_episode passes None until the episode is over, env_utils.py:45-52), so the next
-        `lookahead` steps are computed in ONE launch of the fused n-step kernel (cagpu_rollout_ring) and step(None)
+        `lookahead` steps are computed in ONE launch of the fused n-step kernel (cagpu_step_ex, CaStepEx.ring) and step(None)
         hands out one slot of that ring per call -- same results bit for bit, about half the time per step (a fused
         rollout never waits for the slowest workgroup of a step).  Whatever needs the simulator exactly at the step
         last handed out -- an action, a custom `dt`, reset(), reading an agent's state, episode_stats() -- rewinds
@@ -1038,7 +1038,7 @@ class CollisionAvoidanceEnv(Env):
 
     # ------------------------------------------------------------------ batched extras
     def rollout(self, n_steps):
-        """n_steps x `step(None)` in ONE launch (`cagpu_rollout`): the device-side form of env_utils.run_episode's
+        """n_steps x `step(None)` in ONE launch (`cagpu_step_ex`, CaStepEx.n_steps): the device-side form of env_utils.run_episode's
         `while not terminated: env.step(None)` loop for scenes whose policies are all internal.  Returns the last step's
         (obs, rewards, game_over, False, info); per-episode results accumulate in episode_stats() through the on-device
         auto-reset.  About 1.4x the throughput of n step() calls at 4096 x 10: a fused rollout never waits for the

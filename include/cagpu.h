@@ -248,7 +248,7 @@ typedef struct CaOccGrid {
   double x_width, y_width; /* metres: the window spans [px - x_width / 2, px + x_width / 2) x (py - y_width / 2, py + y_width / 2] */
 } CaOccGrid;
 
-/* Trajectory tape of cagpu_step_traj / cagpu_rollout_traj: the reference's Agent.global_state_history rows
+/* Trajectory tape (CaStepEx.traj; cagpu_step_traj / cagpu_rollout_traj): the reference's Agent.global_state_history rows
  * (agent.py:257-289, appended by Agent.take_action with Config.STORE_HISTORY), written by the step kernels themselves.
  * Step t of a call (t = 0 .. n_steps - 1; a single step: t = 0) writes slot t.  Per (slot, env, agent slot):
  *   - an agent that gets past the done gate of Agent.take_action in this step writes all 12 columns:
@@ -266,7 +266,7 @@ typedef struct CaTraj {
   int32_t *episode;  /* device [n_steps, E] or NULL: CaState.reset_count[e] as the step STARTS (before its auto-reset) */
 } CaTraj;
 
-/* Final record of cagpu_step_final / cagpu_rollout_final: what an auto-reset would otherwise overwrite.  For every env whose
+/* Final record (CaStepEx.fin; cagpu_step_final / cagpu_rollout_final): what an auto-reset would otherwise overwrite.  For every env whose
  * episode ends in a step AND is auto-reset in it (game_over[e] != 0 with a CaAutoReset attached), the step kernel stores,
  * before the reset replaces them,
  *   obs    the env's observation rows of the TERMINAL step, exactly as the step produced them (is_learning column included;
@@ -283,7 +283,7 @@ typedef struct CaFinal {
   uint32_t *flags;  /* device [E, N] (ring: [n_steps, E, N]) or NULL; 4-byte aligned */
 } CaFinal;
 
-/* Episode log of cagpu_step_log / cagpu_rollout_log: one record per FINISHED EPISODE, written by the step kernels at the
+/* Episode log (CaStepEx.log; cagpu_step_log / cagpu_rollout_log): one record per FINISHED EPISODE, written by the step kernels at the
  * auto-reset that would otherwise overwrite it -- the per-episode quantities of the reference's run_episode
  * (experiments/src/env_utils.py:56-87), which CaState.env_stats keeps only as sums.  Every env owns a ring of `capacity`
  * slots; when env e ends its k-th episode (k = CaState.reset_count[e] BEFORE the increment) and is auto-reset in the same
@@ -384,12 +384,65 @@ int cagpu_reset(const CaParams *p, const CaState *s, const CaOut *o, const doubl
  * Agent.take_action + UnicycleDynamics.step + update_ego_frame, _check_for_collisions,
  * _compute_rewards, OtherAgentsStatesSensor.sense + observation assembly, _check_which_agents_done.
  * ext_actions: device float64 [E,N,2], read only for agents with an external policy; may be NULL
- * (the reference's `env.step(None)`, env_utils.py:50).  ar == NULL: no auto-reset. */
+ * (the reference's `env.step(None)`, env_utils.py:50).  ar == NULL: no auto-reset.
+ *
+ * THE GENERAL ENTRY POINT (additive to v12).  Every way of launching the step is one CaStepEx: how many steps, whether every
+ * step keeps its outputs, and which per-call records the kernels read or write beside the state and the CaOut outputs.  The
+ * eleven older names below are fixed conveniences, each equal to one CaStepEx; a NEW per-call record becomes one more
+ * pointer HERE (and one in the kernels' argument block), not another pair of entry points.  A HOST struct like the others,
+ * copied at call time, and so are the records it points to. */
+typedef struct CaStepEx {
+  int32_t n_steps;          /* >= 1 */
+  int32_t ring;             /* != 0: every step keeps its outputs (cagpu_rollout_ring) */
+  int64_t snapshot_delta;   /* ring only */
+  const CaMap    *map;      /* each of the five: NULL = not used */
+  const CaMapSet *set;
+  const CaTraj   *traj;
+  const CaFinal  *fin;
+  const CaEpLog  *log;
+} CaStepEx;                 /* 56 bytes */
+
+/* x == NULL: cagpu_step.  The rules, stated once -- every violation is CA_EINVAL with nothing launched, unless noted:
+ *   n_steps  the steps fused into ONE launch (every step still writes its outputs; with ring == 0 the buffers hold the last
+ *            step's).  Envs never interact, so no grid-wide sync is needed: the batched form of env_utils.py:45-52
+ *            `while not terminated: env.step(None)`.  ext_actions (if any) are held constant over the n_steps.  n_steps < 1
+ *            is rejected.  The per-step inputs CaState.rvo_collab / rvo_heading_noise / ext_state belong to the ONE step that
+ *            consumes them: any of them set with n_steps > 1 or ring is rejected.
+ *   ring     != 0: the output pointers of `o` name slot 0 of a ring of n_steps slots and step t of the call writes slot t
+ *            (cagpu_rollout_ring has the layout); state, statistics and auto-resets are those of ring == 0.
+ *   snapshot_delta  the ring's rewind point (cagpu_rollout_ring): != 0 without ring is rejected; with ring but without the
+ *            pipelined n-step kernel (cagpu_ring_snapshots() != 1) it is CA_EUNSUPPORTED.
+ *   map      a static map: an agent whose disc covers an occupied static cell collides with the wall
+ *            (collision_avoidance_env.py:494-506, :425-429).  map->static_bits == NULL: as without a map; otherwise rows,
+ *            cols >= 1 and cell > 0.
+ *   set      a map per env (CaMapSet; cagpu_step_maps has the semantics): set->env_map or set->map.static_bits NULL,
+ *            num_maps < 1 or a bad geometry is rejected.
+ *            map and set at once is rejected.  Either of them with n_steps > 1 or ring is rejected: the n-step kernels take
+ *            no map, and no older entry point reaches such a launch.
+ *   traj     the trajectory tape (CaTraj): step t of the call records slot t.  traj->rows NULL or not 16-byte aligned, or
+ *            traj->episode not 4-byte aligned, is rejected.
+ *   fin      the final record (CaFinal) of every env that auto-resets.  fin->obs NULL or not 16-byte aligned,
+ *            fin->flags not 4-byte aligned, or fin without ar (nothing is ever overwritten then) is rejected.
+ *   log      the episode log (CaEpLog).  log->rows or log->head NULL or not 16-byte aligned, capacity < 1, or log without ar
+ *            (no episode is ever logged then) is rejected.
+ * A call that is wrong in several ways reports the first of: map and set at once, snapshot_delta without ring, the log,
+ * the final record, the tape, params / state / out, the rest.
+ * The records change neither the kernel selection nor grid and block: state, outputs and statistics are bit-identical with
+ * and without them, and every kernel family (the general, the pipelined single- and n-step and the large-env kernel) writes
+ * all three -- the pipelined kernels keep the final record and the log through their " final" instantiations (a template
+ * flag; the log behind a uniform test of its pointers inside), the general kernel on both of its reset paths (reset_obs copy
+ * / second sensing pass), the general and the large-env kernel behind uniform tests, always with ordinary stores from the
+ * lanes that hold the values.  cagpu_last_kernel() shows " traj" / " final" / " log" behind the pipelined kernel's name.  A
+ * ring launch logs the episodes of steps that are not handed out yet; a replay from a rewind point rewrites the same
+ * records bit for bit. */
+int cagpu_step_ex(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
+                  const CaStepEx *x, void *stream);
+
+/* = cagpu_step_ex with x == NULL (n_steps = 1, no ring, no record). */
 int cagpu_step(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                void *stream);
 
-/* cagpu_step with a static map: an agent whose disc covers an occupied static cell collides with the wall
- * (collision_avoidance_env.py:494-506, :425-429).  map == NULL or map->static_bits == NULL: same as cagpu_step. */
+/* = CaStepEx{n_steps = 1, map}.  map == NULL: cagpu_step. */
 int cagpu_step_map(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                    const CaMap *map, void *stream);
 
@@ -404,9 +457,9 @@ int cagpu_laserscan(const CaParams *p, const CaState *s, const CaMap *map, const
 /* cagpu_step_map / cagpu_laserscan with a map set (v12): every env tests its walls against, and scans, its OWN map
  * env_map[e].  With set->map_seed != 0 an auto-reset draws the env's next map (CaMapSet.map_seed); the wall test of the
  * terminal step still uses the old map, the next step and the next scan the new one (the reference's reset observation
- * already sees the new map).  CA_EINVAL, nothing launched: set, set->env_map or set->map.static_bits NULL,
- * num_maps < 1, or a bad geometry.  Envs with more than 64 agents, the pipelined and the plain step kernels all take a
- * set; cagpu_rollout / cagpu_rollout_ring do not. */
+ * already sees the new map).  Envs with more than 64 agents, the pipelined and the plain step kernels all take a set; the
+ * n-step kernels do not.  cagpu_step_maps = CaStepEx{n_steps = 1, set}; additionally `set` may not be NULL.
+ * cagpu_laserscan_maps: CA_EINVAL, nothing launched, for a NULL set and for what cagpu_step_ex rejects of a set. */
 int cagpu_step_maps(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                     const CaMapSet *set, void *stream);
 int cagpu_laserscan_maps(const CaParams *p, const CaState *s, const CaMapSet *set, const CaScan *scan, void *stream);
@@ -502,11 +555,7 @@ int cagpu_generate_cases_ragged(int64_t num_cases, int32_t max_agents, int32_t n
                                 double radius_lo, double radius_hi, uint64_t seed, double *cases, int32_t *counts,
                                 int32_t *status, void *stream);
 
-/* n_steps consecutive cagpu_step calls fused into ONE launch (every step still writes its
- * outputs; the buffers hold the last step's).  Envs never interact, so no grid-wide sync is
- * needed.  This is the batched form of env_utils.py:45-52 `while not terminated: env.step(None)`.
- * ext_actions (if any) are held constant over the n_steps.  The per-step inputs CaState.rvo_collab / rvo_heading_noise /
- * ext_state belong to the ONE step that consumes them: with n_steps > 1 any of them set is CA_EINVAL. */
+/* n_steps consecutive cagpu_step calls fused into ONE launch: = CaStepEx{n_steps}. */
 int cagpu_rollout(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions,
                   const CaAutoReset *ar, int32_t n_steps, void *stream);
 
@@ -518,8 +567,7 @@ int cagpu_rollout(const CaParams *p, const CaState *s, const CaOut *o, const dou
  *   o->obs [n_steps, E, N, 6+7K], o->rewards [n_steps, E, N], o->done [n_steps, E, N], o->game_over [n_steps, E],
  *   o->actions / o->orca_vel (if given) [n_steps, E, N, 2].
  * State, statistics and auto-resets are those of cagpu_rollout(n_steps) -- i.e. of n_steps cagpu_step calls, bit for bit
- * (tests/test_gpu_ring.py).  Like cagpu_rollout it takes no per-step inputs (CaState.rvo_collab / rvo_heading_noise /
- * ext_state must be NULL: CA_EINVAL; ext_actions, if any, are held constant).
+ * (tests/test_gpu_ring.py).  = CaStepEx{n_steps, ring = 1, snapshot_delta}.
  * snapshot_delta (bytes; 0 = none): the REWIND POINT.  A caller that runs ahead must be able to go back (an action arrives
  * for step t < n_steps: restore the state the call started from, cagpu_rollout(t), go on one step at a time).  With all state
  * arrays of `s` in ONE allocation and a second allocation of the same layout snapshot_delta bytes away, the kernel itself
@@ -533,42 +581,29 @@ int cagpu_rollout_ring(const CaParams *p, const CaState *s, const CaOut *o, cons
  * 0: it does not; < 0: the arguments are invalid (CA_E*).  Host-only, launches nothing. */
 int cagpu_ring_snapshots(const CaParams *p, const CaState *s, const CaOut *o, const CaAutoReset *ar, int32_t n_steps);
 
-/* The step / rollout calls that also RECORD every agent's trajectory row (CaTraj), in the same kernels and with the same
- * kernel selection, grid and block as the calls they mirror -- state, outputs and statistics are bit-identical to those:
- *   cagpu_step_traj     = cagpu_step (map == set == NULL) / cagpu_step_map (map) / cagpu_step_maps (set); at most one of
- *                         `map`, `set` may be non-NULL; records slot 0.
- *   cagpu_rollout_traj  = cagpu_rollout (ring == 0) / cagpu_rollout_ring (ring != 0, with its snapshot_delta); records
- *                         n_steps slots.
- * Every kernel family records (the general, the pipelined single- and n-step and the large-env kernel).  CA_EINVAL, nothing
- * launched: traj or traj->rows NULL, rows not 16-byte aligned, episode not 4-byte aligned, both map and set given -- plus
- * whatever the mirrored call rejects.  cagpu_last_kernel() shows " traj" behind the pipelined kernel's name. */
+/* The step / rollout calls that also RECORD every agent's trajectory row (CaTraj):
+ *   cagpu_step_traj     = CaStepEx{n_steps = 1, map, set, traj}
+ *   cagpu_rollout_traj  = CaStepEx{n_steps, ring, snapshot_delta, traj}
+ * Additionally `traj` may not be NULL. */
 int cagpu_step_traj(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                     const CaMap *map, const CaMapSet *set, const CaTraj *traj, void *stream);
 int cagpu_rollout_traj(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                        int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj *traj, void *stream);
 
-/* The step / rollout calls that also keep the FINAL RECORD (CaFinal) of every env that auto-resets, and -- `traj` may be
- * NULL -- record the trajectory tape as well: cagpu_step_traj / cagpu_rollout_traj with one more argument, the same kernel
- * selection, grid and block; state, outputs, statistics (and the tape) are bit-identical to the calls they mirror.  Every
- * kernel that auto-resets keeps the record: the pipelined kernels (a template flag: cagpu_last_kernel() shows " final"
- * behind the name), the general kernel on both of its reset paths (reset_obs copy / second sensing pass) and the large-env
- * kernel.  CA_EINVAL, nothing launched: fin or fin->obs NULL, fin->obs not 16-byte / fin->flags not 4-byte aligned, fin
- * without ar (nothing is ever overwritten then) -- plus whatever the mirrored call rejects. */
+/* The step / rollout calls that also keep the FINAL RECORD (CaFinal), with or without the tape:
+ *   cagpu_step_final    = CaStepEx{n_steps = 1, map, set, traj, fin}
+ *   cagpu_rollout_final = CaStepEx{n_steps, ring, snapshot_delta, traj, fin}
+ * Additionally `fin` may not be NULL (`traj` may). */
 int cagpu_step_final(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                      const CaMap *map, const CaMapSet *set, const CaTraj *traj, const CaFinal *fin, void *stream);
 int cagpu_rollout_final(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                         int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj *traj, const CaFinal *fin,
                         void *stream);
 
-/* The step / rollout calls that also write the EPISODE LOG (CaEpLog): supersets of cagpu_step_final / cagpu_rollout_final
- * -- `traj` and `fin` may each be NULL, `log` may not --, the same kernel selection, grid and block; state, outputs,
- * statistics (and the tape, and the final record) are bit-identical to the calls they mirror.  Every kernel that auto-resets
- * writes it, with ordinary stores from the lanes that hold the values: the pipelined kernels through their " final"
- * instantiations (a uniform test of the log pointers inside; cagpu_last_kernel() shows " log" behind the name), the general
- * and the large-env kernel behind a uniform test.  A ring launch logs the episodes of steps that are not handed out yet; a
- * replay from a rewind point rewrites the same records bit for bit.  CA_EINVAL, nothing launched: log, log->rows or
- * log->head NULL, either not 16-byte aligned, capacity < 1, log without ar (no episode is ever logged then), both map and
- * set given, snapshot_delta without ring -- plus whatever the mirrored call rejects. */
+/* The step / rollout calls that also write the EPISODE LOG (CaEpLog), with or without the tape and the final record:
+ *   cagpu_step_log      = CaStepEx{n_steps = 1, map, set, traj, fin, log}
+ *   cagpu_rollout_log   = CaStepEx{n_steps, ring, snapshot_delta, traj, fin, log}
+ * Additionally `log` may not be NULL (`traj` and `fin` may). */
 int cagpu_step_log(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                    const CaMap *map, const CaMapSet *set, const CaTraj *traj, const CaFinal *fin, const CaEpLog *log,
                    void *stream);

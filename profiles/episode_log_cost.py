@@ -2,14 +2,14 @@
 """What the episode log (BatchedSim.log_episodes / env.log_episodes) costs: 4096 x 10 RVO agents, fixture cases with
 auto-reset, `step_lookahead()` from a ring of 20 --
 
-  off   the log never enabled (the product path as it was: cagpu_rollout_ring)
+  off   the log never enabled (the product path as it was: cagpu_step_ex with CaStepEx.ring, no record)
   on    log_episodes(): the step kernels store a 32-byte row per agent and a 16-byte head per env for every env that
-        auto-resets (cagpu_rollout_log, the " final" instantiation of the pipelined kernel with a uniform test inside)
+        auto-resets (CaStepEx.log, the " final" instantiation of the pipelined kernel with a uniform test inside)
   drain on + one episodes() call per block (a host synchronisation and a handful of torch kernels per drain)
 
 Device events around blocks of steps, >= --seconds per mode after a warm-up, the modes ALTERNATE block by block in one
 process so that clock drift hits all alike; the median block of each mode and the spread of the blocks are reported.
-`--modes off` measures a library without the entry points (the parent commit's build, named by CAGPU_LIB) with the same
+`--modes off` measures a library without the record (the parent commit's build, named by CAGPU_LIB) with the same
 command.  One JSON line on stdout.
 
     python profiles/episode_log_cost.py [--envs 4096] [--ring 20] [--seconds 0.6] [--modes off,on,drain]

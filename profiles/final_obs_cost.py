@@ -2,13 +2,13 @@
 """What the final record (BatchedSim.keep_final / env.keep_final_observations) costs: 4096 x 10 RVO agents, fixture cases
 with auto-reset, `step_lookahead()` from a ring of 20 --
 
-  off   the record never enabled (the product path as it was: cagpu_rollout_ring)
+  off   the record never enabled (the product path as it was: cagpu_step_ex with CaStepEx.ring, no record)
   on    keep_final(): every ring slot carries its final block, the step kernels save the terminal rows / flag words of
-        the envs that auto-reset (cagpu_rollout_final)
+        the envs that auto-reset (CaStepEx.fin)
 
 Synchronised wall clock around blocks of steps, >= --seconds per mode after a warm-up, modes interleaved block by block so
 that clock drift hits both alike; the median block of each mode is reported.  `--modes off` measures a library without the
-entry points (the parent commit's build, named by CAGPU_LIB) with the same command.  `--env`: also the env API's default
+record (the parent commit's build, named by CAGPU_LIB) with the same command.  `--env`: also the env API's default
 adaptive ring with the record off / on -- the longest ring its byte budget allows, the length it settled on, us per step.
 One JSON line on stdout.
 
