@@ -110,13 +110,22 @@ class CaNet(C.Structure):
                                                 ("reserved0", C.c_int32), ("packed", _P)]
 
 
+class CaNetQuery(C.Structure):
+    _fields_ = [("x", _P), ("rows", C.c_int64), ("width", C.c_int32), ("reserved0", C.c_int32), ("value_kernel", _P),
+                ("value_bias", _P), ("logits", _P), ("value", _P), ("action", _P)]
+
+
+class CaNetValue(C.Structure):
+    _fields_ = [("value_kernel", _P), ("value_bias", _P), ("value", _P)]
+
+
 EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_reset", "cagpu_step", "cagpu_step_map", "cagpu_rollout",
            "cagpu_orca", "cagpu_observe", "cagpu_laserscan", "cagpu_ga3c", "cagpu_generate_cases", "cagpu_generate_cases_ragged", "cagpu_plan", "cagpu_debug_libm", "cagpu_device_faults", "cagpu_workspace_bytes",
            "cagpu_ga3c_packed_bytes", "cagpu_ga3c_pack", "cagpu_rollout_ring", "cagpu_ring_snapshots", "cagpu_debug_copy8", "cagpu_device_faults_async",
            "cagpu_step_maps", "cagpu_laserscan_maps", "cagpu_occupancy_grid", "cagpu_occupancy_grid_maps",
            "cagpu_step_traj", "cagpu_rollout_traj", "cagpu_step_final", "cagpu_rollout_final",
            "cagpu_step_log", "cagpu_rollout_log", "cagpu_step_ex",
-           "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes")
+           "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes", "cagpu_ga3c_query", "cagpu_ga3c_value")
 
 _lib = None
 
@@ -173,6 +182,8 @@ def lib():
     L.cagpu_orca.argtypes = [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int32,
                              C.c_float, _P, _P]
     L.cagpu_ga3c.argtypes = [PP, PS, _P, C.POINTER(CaNet), _P, _P, _P]
+    L.cagpu_ga3c_query.argtypes = [C.POINTER(CaNet), C.POINTER(CaNetQuery), _P]
+    L.cagpu_ga3c_value.argtypes = [PP, PS, _P, C.POINTER(CaNet), _P, _P, C.POINTER(CaNetValue), _P]
     L.cagpu_generate_cases.argtypes = [C.c_int64, C.c_int32] + [C.c_double] * 6 + [C.c_uint64, _P, _P, _P]
     L.cagpu_generate_cases_ragged.argtypes = ([C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32] + [C.c_double] * 4 +
                                               [C.c_uint64, _P, _P, _P, _P])

@@ -152,6 +152,7 @@ class BatchedSim(object):
         self._has_ga3c = False    # some agent's policy is CA_POL_GA3C_CADRL (set_plugins)
         self._ga3c_ext = None
         self.ga3c_logits = None
+        self.ga3c_value = None    # float32 [E, N] (load_ga3c(keep_value=True)): logits_v of the agents ga3c() evaluated
         self._fault = None        # the non-blocking fault-word probe of the product path (_fault_probe)
         # (the first probe -- it creates the side stream and the pinned word: milliseconds -- on the second launch of a
         # simulator's life, not 256 launches in, in the middle of somebody's timed loop)
@@ -328,29 +329,20 @@ class BatchedSim(object):
         """number of agents the last ga3c() call evaluated (device -> host read: synchronises)"""
         return int(self._net_tensors["rows_scratch"][self.E * self.N].item())
 
-    def load_ga3c(self, weights=None, keep_logits=False, index=0):
+    def load_ga3c(self, weights=None, keep_logits=False, index=0, keep_value=False):
         """Upload the GA3C-CADRL network (GA3CCADRLPolicy.initialize_network, GA3CCADRLPolicy.py:23-47).  `weights`:
         an .npz written by oracle/extract_ga3c_weights.py (default: the shipped IROS18/network_01900000, the
         reference's default checkpoint) or a dict of float32 arrays with the same keys.
         `index`: several checkpoints may be loaded side by side (index 0, 1, ...); set_ga3c_assignment() says which agent
         runs which (the reference gives every agent its own policy object and session).  Without an assignment every
-        GA3C-CADRL agent runs checkpoint 0."""
+        GA3C-CADRL agent runs checkpoint 0.
+        keep_value: also evaluate the network's value head (logits_v_kernel / logits_v_bias of the weights, the graph's
+        `Squeeze:0`) in the same launch; `ga3c_value` [E, N] then holds it for the agents ga3c() evaluated (other entries
+        keep what they held).  ValueError if the weights carry no value head."""
         self.sync()
-        if weights is None:
-            weights = GA3C_DEFAULT_WEIGHTS
-        if isinstance(weights, str):
-            with np.load(weights) as z:
-                weights = {k: z[k] for k in z.files}
-        names = {"logits_kernel": "logits_p_kernel", "logits_bias": "logits_p_bias"}
-        shapes = {"lstm_kernel": (71, 256), "lstm_bias": (256,), "layer1_kernel": (68, 256), "layer1_bias": (256,),
-                  "layer2_kernel": (256, 256), "layer2_bias": (256,), "fc1_kernel": (256, 256), "fc1_bias": (256,),
-                  "logits_kernel": (256, 11), "logits_bias": (11,), "input_mean": (138,), "input_std": (138,)}
-        ts = {}
-        for f in nat.NET_FIELDS:
-            a = np.ascontiguousarray(weights[names.get(f, f)], dtype=np.float32)
-            if a.shape != shapes[f]:
-                raise ValueError("GA3C-CADRL weight %s has shape %s, expected %s" % (f, a.shape, shapes[f]))
-            ts[f] = torch.from_numpy(a).to(self.device)
+        ts = _ga3c_weight_tensors(weights, self.device)
+        if keep_value and "value_kernel" not in ts:
+            raise ValueError("keep_value=True, but these GA3C-CADRL weights have no logits_v_kernel / logits_v_bias")
         # scratch of cagpu_ga3c: the packed list of the agents that need an action this step (+ their count)
         ts["rows_scratch"] = torch.empty((self.E * self.N + 6,), dtype=torch.int32, device=self.device)
         # the four big matrices as fp16 planes in matrix-core fragment order: split once per checkpoint on the device
@@ -363,6 +355,8 @@ class BatchedSim(object):
         if keep_logits or self.ga3c_logits is None:
             self.ga3c_logits = torch.zeros((self.E, self.N, 11), dtype=torch.float32, device=self.device) \
                 if keep_logits else None
+        if keep_value and self.ga3c_value is None:
+            self.ga3c_value = torch.zeros((self.E, self.N), dtype=torch.float32, device=self.device)
 
     def set_ga3c_assignment(self, index):
         """index: int array broadcastable to [E, N] -- the checkpoint (load_ga3c(..., index=)) each GA3C-CADRL agent runs;
@@ -396,6 +390,8 @@ class BatchedSim(object):
         if fused and (self.N > 32 or self.p.sort_mode == nat.SORT_TIME_TO_IMPACT or self._variants):
             fused = False
         obs_ptr = None if fused else self._obs.data_ptr()
+        if self.ga3c_value is not None:
+            return self._ga3c_with_value(ext, obs_ptr, lg)
         if self._agent_net is None:      # one checkpoint (index 0) for every GA3C-CADRL agent
             nat.check(self.lib.cagpu_ga3c(C.byref(self.p), C.byref(self._cs), obs_ptr, C.byref(self._net),
                                           ext.data_ptr(), lg, self._stream()))
@@ -406,6 +402,28 @@ class BatchedSim(object):
             nat.check(self.lib.cagpu_ga3c(C.byref(self.p), C.byref(self._cs), obs_ptr, C.byref(net),
                                           ext.data_ptr(), lg, self._stream()))
             net.agent_net = None
+        return ext
+
+    def _ga3c_with_value(self, ext, obs_ptr, lg):
+        """ga3c() with the value head (load_ga3c(keep_value=True)): cagpu_ga3c_value instead of cagpu_ga3c, the same
+        launches otherwise; every checkpoint writes the value of its own agents into ga3c_value"""
+        def launch(net, ts):
+            if "value_kernel" not in ts:
+                raise ValueError("ga3c_value is kept, but a loaded GA3C-CADRL checkpoint has no value head")
+            v = nat.CaNetValue(value_kernel=ts["value_kernel"].data_ptr(), value_bias=ts["value_bias"].data_ptr(),
+                               value=self.ga3c_value.data_ptr())
+            nat.check(self.lib.cagpu_ga3c_value(C.byref(self.p), C.byref(self._cs), obs_ptr, C.byref(net), ext.data_ptr(), lg,
+                                                C.byref(v), self._stream()))
+        if self._agent_net is None:
+            launch(self._net, self._net_tensors)
+            return ext
+        for idx in sorted(self._nets):
+            net, ts = self._nets[idx]
+            net.agent_net, net.net_index = self._agent_net.data_ptr(), idx
+            try:
+                launch(net, ts)
+            finally:
+                net.agent_net = None
         return ext
 
     def generate_cases(self, num_cases, seed, side_length=4.0, speed_bnds=(0.5, 2.0), radius_bnds=(0.2, 0.8),
@@ -1322,6 +1340,114 @@ class BatchedSim(object):
         if check:
             self.check_faults()
         return self._state["env_stats"].sum(dim=0)
+
+
+_GA3C_NAMES = {"logits_kernel": "logits_p_kernel", "logits_bias": "logits_p_bias"}
+_GA3C_SHAPES = {"lstm_kernel": (71, 256), "lstm_bias": (256,), "layer1_kernel": (68, 256), "layer1_bias": (256,),
+                "layer2_kernel": (256, 256), "layer2_bias": (256,), "fc1_kernel": (256, 256), "fc1_bias": (256,),
+                "logits_kernel": (256, 11), "logits_bias": (11,), "input_mean": (138,), "input_std": (138,)}
+
+
+def _ga3c_weight_tensors(weights, device):
+    """weights (None = the shipped default, an .npz path, or a dict of float32 arrays) -> {CaNet field: device tensor},
+    plus value_kernel [256] / value_bias [1] where the weights carry logits_v_*"""
+    if weights is None:
+        weights = GA3C_DEFAULT_WEIGHTS
+    if isinstance(weights, str):
+        with np.load(weights) as z:
+            weights = {k: z[k] for k in z.files}
+    ts = {}
+    for f in nat.NET_FIELDS:
+        a = np.ascontiguousarray(weights[_GA3C_NAMES.get(f, f)], dtype=np.float32)
+        if a.shape != _GA3C_SHAPES[f]:
+            raise ValueError("GA3C-CADRL weight %s has shape %s, expected %s" % (f, a.shape, _GA3C_SHAPES[f]))
+        ts[f] = torch.from_numpy(a).to(device)
+    if "logits_v_kernel" in weights and "logits_v_bias" in weights:
+        k = np.ascontiguousarray(weights["logits_v_kernel"], dtype=np.float32)
+        b = np.ascontiguousarray(weights["logits_v_bias"], dtype=np.float32)
+        if k.shape != (256, 1) or b.shape != (1,):
+            raise ValueError("GA3C-CADRL weight logits_v has shapes %s / %s, expected (256, 1) / (1,)" % (k.shape, b.shape))
+        ts["value_kernel"] = torch.from_numpy(k.reshape(256)).to(device)
+        ts["value_bias"] = torch.from_numpy(b).to(device)
+    return ts
+
+
+# (device, checkpoint) -> (CaNet, its tensors, the weights object).  A checkpoint given as a path is keyed by the path; one
+# given as a dict by the dict's IDENTITY (the entry holds the dict, so the id stays its own): a dict changed in place after
+# its first query is NOT re-uploaded -- pass a new dict, or call ga3c_query_forget().  Each entry pins 1.3 MB of device
+# memory (weights + packed planes); the cache holds the _QUERY_NETS_MAX most recently used and drops the oldest.
+_query_nets = {}
+_QUERY_NETS_MAX = 16
+
+
+def ga3c_query_forget():
+    """drop every cached device copy of ga3c_query's networks (their memory goes back once no launch uses it)"""
+    _query_nets.clear()
+
+
+def _query_net(weights, device):
+    """the uploaded + packed network of ga3c_query, cached per (device, checkpoint): a path by its name, a dict by identity"""
+    if weights is None:
+        weights = GA3C_DEFAULT_WEIGHTS
+    key = (str(device), weights if isinstance(weights, str) else id(weights))
+    hit = _query_nets.pop(key, None)   # (re-inserted below: the dict's order is the order of last use)
+    if hit is None:
+        L = nat.lib()
+        ts = _ga3c_weight_tensors(weights, device)
+        ts["packed"] = torch.empty((int(L.cagpu_ga3c_packed_bytes()),), dtype=torch.uint8, device=device)
+        net = nat.CaNet(**{f: ts[f].data_ptr() for f in nat.NET_FIELDS + ("packed",)})
+        with torch.cuda.device(device):
+            st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            nat.check(L.cagpu_ga3c_pack(C.byref(net), ts["packed"].data_ptr(), ts["packed"].numel(), st))
+        hit = (net, ts, weights)
+        while len(_query_nets) >= _QUERY_NETS_MAX:
+            _query_nets.pop(next(iter(_query_nets)))
+    _query_nets[key] = hit
+    return hit
+
+
+def ga3c_query(x, weights=None, want=("logits", "value", "action"), device=None):
+    """The GA3C-CADRL network on given rows, without a simulator (cagpu_ga3c_query; NetworkVPCore.predict_p and the value
+    fetch of GA3C_CADRL/network.py:24-41, :74).  x: [rows, width] policy vectors X = obs[1:] -- a float32 device tensor is
+    read in place, anything else (numpy, lists, other dtypes / devices) is copied to `device` (default: x's own device if
+    it is a GPU tensor, else cuda:0); width is cropped / zero-padded to 138 as crop_x does.  weights: as load_ga3c (the
+    packed weights are cached per device and checkpoint).  want: which of "logits" [rows, 11], "value" [rows], "action"
+    int32 [rows] (first maximum) to compute.  Returns {name: device tensor}."""
+    want = tuple(want)
+    bad = set(want) - {"logits", "value", "action"}
+    if bad or not want:
+        raise ValueError("ga3c_query: want must name some of logits / value / action, got %r" % (want,))
+    if device is None:
+        device = x.device if (torch.is_tensor(x) and x.is_cuda) else "cuda:0"
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    xt = torch.as_tensor(x)
+    if xt.dim() != 2 or xt.shape[1] < 1:
+        raise ValueError("ga3c_query: x must be [rows, width >= 1], got shape %s" % (tuple(xt.shape),))
+    xt = xt.to(device=device, dtype=torch.float32).contiguous()
+    net, ts, _ = _query_net(weights, device)
+    rows = int(xt.shape[0])
+    out = {}
+    if "logits" in want:
+        out["logits"] = torch.empty((rows, 11), dtype=torch.float32, device=device)
+    if "value" in want:
+        if "value_kernel" not in ts:
+            raise ValueError("ga3c_query: these GA3C-CADRL weights have no logits_v_kernel / logits_v_bias (value head)")
+        out["value"] = torch.empty((rows,), dtype=torch.float32, device=device)
+    if "action" in want:
+        out["action"] = torch.empty((rows,), dtype=torch.int32, device=device)
+    if rows == 0:   # (an empty tensor has no address to hand over; the C entry point would launch nothing either)
+        return out
+    ptr = lambda n: out[n].data_ptr() if n in out else None
+    q = nat.CaNetQuery(x=xt.data_ptr(), rows=rows, width=int(xt.shape[1]),
+                       value_kernel=ts["value_kernel"].data_ptr() if "value" in out else None,
+                       value_bias=ts["value_bias"].data_ptr() if "value" in out else None,
+                       logits=ptr("logits"), value=ptr("value"), action=ptr("action"))
+    with torch.cuda.device(device):
+        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        nat.check(nat.lib().cagpu_ga3c_query(C.byref(net), C.byref(q), st))
+    return out
 
 
 def orca(pos, vel, pref, radius, max_speed, collab=0.5, time_horizon=5.0, time_step=0.1, max_neighbors=None,

@@ -2587,8 +2587,96 @@ int cagpu_render_maps(const CaParams* p, const CaState* s, const CaMapSet* set, 
   return render_impl(p, s, &set->map, r, stream, set);
 }
 
+namespace {
+constexpr size_t ga3c_lds_bytes() {
+#if defined(CAGPU_GA3C_SOLO)   // timing experiment (scratch/ga3c_phases.py): one workgroup per CU, a wave has its SIMD to itself
+  return 100 * 1024;
+#else
+  return ga3c::LDS_BYTES;
+#endif
+}
+int ga3c_check_net(const CaNet* net) {
+  const void* w[] = {net->lstm_kernel, net->lstm_bias, net->layer1_kernel, net->layer1_bias, net->layer2_kernel,
+                     net->layer2_bias, net->fc1_kernel, net->fc1_bias, net->logits_kernel, net->logits_bias,
+                     net->input_mean, net->input_std};
+  for (const void* q : w)
+    if (!q || (reinterpret_cast<uintptr_t>(q) & 15)) return fail(CA_EINVAL, "cagpu_ga3c: NULL or not 16-byte aligned weight pointer%s");
+  if (!net->packed || (reinterpret_cast<uintptr_t>(net->packed) & 15))
+    return fail(CA_EINVAL, "cagpu_ga3c: CaNet.packed is NULL or not 16-byte aligned (fill it once per checkpoint with cagpu_ga3c_pack)%s");
+  return CA_OK;
+}
+// The launch of ga3c_kernel<true> (the query rows / the value head): its own instantiation, its own LDS attribute.
+int ga3c_launch_ext(ga3c::Args& k, const ga3c::Ext& ex, void* stream) {
+  static thread_local bool lds_raised[16] = {false};
+  int dev_id = 0;
+  (void)hipGetDevice(&dev_id);
+  hipError_t e = hipSuccess;
+  if (!lds_raised[dev_id & 15]) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ga3c::ga3c_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(ga3c_lds_bytes()));
+    if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    lds_raised[dev_id & 15] = true;
+  }
+  k.slots = 2 * device_cus();
+  k.force_tile = 0;
+#if defined(CAGPU_KNOBS)
+  if (const char* ft = std::getenv("CAGPU_GA3C_TILE")) k.force_tile = std::atoi(ft);
+#endif
+  const unsigned grid = static_cast<unsigned>((k.B + 31) / 32);  // (B < 2^31)
+  std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ga3c_kernel<true> %s grid=%u lds=%zu rows=%ld width=%d%s%s%s",
+                ex.query ? "query" : "sim", grid, ga3c_lds_bytes(), k.B, k.W - 1, k.logits ? " logits" : "",
+                ex.value ? " value" : "", ex.action ? " action" : "");
+  hipLaunchKernelGGL(ga3c::ga3c_kernel<true>, dim3(grid), dim3(ga3c::NT), ga3c_lds_bytes(), static_cast<hipStream_t>(stream), k, ex);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
+}
+int ga3c_impl(const CaParams* p, const CaState* s, const float* obs, const CaNet* net, double* ext_actions, float* logits,
+              const CaNetValue* val, void* stream);
+}  // namespace
+
 int cagpu_ga3c(const CaParams* p, const CaState* s, const float* obs, const CaNet* net, double* ext_actions, float* logits,
                void* stream) {
+  return ga3c_impl(p, s, obs, net, ext_actions, logits, nullptr, stream);
+}
+
+int cagpu_ga3c_value(const CaParams* p, const CaState* s, const float* obs, const CaNet* net, double* ext_actions, float* logits,
+                     const CaNetValue* v, void* stream) {
+  if (v && (!v->value || !v->value_kernel || !v->value_bias))
+    return fail(CA_EINVAL, "cagpu_ga3c_value: CaNetValue needs value, value_kernel and value_bias%s");
+  if (v && p && static_cast<long>(p->num_envs) * p->num_agents >= (1L << 31))  // (the value launch indexes rows as int32)
+    return fail(CA_EUNSUPPORTED, "cagpu_ga3c_value: more than 2^31 agents%s");
+  return ga3c_impl(p, s, obs, net, ext_actions, logits, v, stream);
+}
+
+int cagpu_ga3c_query(const CaNet* net, const CaNetQuery* q, void* stream) {
+  if (!net || !q || !q->x) return fail(CA_EINVAL, "cagpu_ga3c_query: NULL argument%s");
+  if (q->rows < 0 || q->width < 1) return fail(CA_EINVAL, "cagpu_ga3c_query: rows must be >= 0 and width >= 1%s");
+  if (q->value && (!q->value_kernel || !q->value_bias))
+    return fail(CA_EINVAL, "cagpu_ga3c_query: value needs value_kernel and value_bias (logits_v)%s");
+  if (!q->logits && !q->value && !q->action) return fail(CA_EINVAL, "cagpu_ga3c_query: no output requested%s");
+  if (const int rc = ga3c_check_net(net)) return rc;
+  if (q->rows == 0) return CA_OK;
+  if (q->rows >= (1LL << 31)) return fail(CA_EUNSUPPORTED, "cagpu_ga3c_query: 2^31 rows or more in one call%s");
+  ga3c::Args k;
+  std::memset(&k, 0, sizeof(k));
+  k.obs = q->x;
+  k.B = static_cast<long>(q->rows);
+  k.W = q->width + 1;  // (the kernel's W counts the is_learning column a query row does not have)
+  k.net = *net;
+  k.net.agent_net = nullptr;
+  k.logits = q->logits;
+  ga3c::Ext ex;
+  std::memset(&ex, 0, sizeof(ex));
+  ex.query = 1;
+  if (q->value) { ex.value_kernel = q->value_kernel; ex.value_bias = q->value_bias; ex.value = q->value; }
+  ex.action = q->action;
+  return ga3c_launch_ext(k, ex, stream);
+}
+
+namespace {
+int ga3c_impl(const CaParams* p, const CaState* s, const float* obs, const CaNet* net, double* ext_actions, float* logits,
+              const CaNetValue* val, void* stream) {
   if (!p || !s || !net || !ext_actions) return fail(CA_EINVAL, "cagpu_ga3c: NULL argument%s");
   if (!obs) {  // fused sensing: the kernel computes the observation rows it needs from the state
     if (p->num_agents > 32 || p->sort_mode == CA_SORT_TIME_TO_IMPACT)
@@ -2600,13 +2688,7 @@ int cagpu_ga3c(const CaParams* p, const CaState* s, const float* obs, const CaNe
   }
   if (p->num_envs < 1 || p->num_agents < 1 || p->max_obs < 0) return fail(CA_EINVAL, "cagpu_ga3c: bad sizes%s");
   if (!s->flags) return fail(CA_EINVAL, "cagpu_ga3c: NULL state pointer%s");
-  const void* w[] = {net->lstm_kernel, net->lstm_bias, net->layer1_kernel, net->layer1_bias, net->layer2_kernel,
-                     net->layer2_bias, net->fc1_kernel, net->fc1_bias, net->logits_kernel, net->logits_bias,
-                     net->input_mean, net->input_std};
-  for (const void* q : w)
-    if (!q || (reinterpret_cast<uintptr_t>(q) & 15)) return fail(CA_EINVAL, "cagpu_ga3c: NULL or not 16-byte aligned weight pointer%s");
-  if (!net->packed || (reinterpret_cast<uintptr_t>(net->packed) & 15))
-    return fail(CA_EINVAL, "cagpu_ga3c: CaNet.packed is NULL or not 16-byte aligned (fill it once per checkpoint with cagpu_ga3c_pack)%s");
+  if (const int rc = ga3c_check_net(net)) return rc;
   ga3c::Args k;
   std::memset(&k, 0, sizeof(k));
   k.obs = obs; k.flags = s->flags;
@@ -2628,17 +2710,19 @@ int cagpu_ga3c(const CaParams* p, const CaState* s, const float* obs, const CaNe
                        net->net_index, epoch);
   }
   static_assert(ga3c::LDS_BYTES <= 80 * 1024, "two workgroups per CU");
-#if defined(CAGPU_GA3C_SOLO)   // timing experiment (scratch/ga3c_phases.py): one workgroup per CU, a wave has its SIMD to itself
-  constexpr size_t GA3C_LDS = 100 * 1024;
-#else
-  constexpr size_t GA3C_LDS = ga3c::LDS_BYTES;
-#endif
+  constexpr size_t GA3C_LDS = ga3c_lds_bytes();
+  if (val) {  // the value head rides on the other instantiation; the default launch below is untouched
+    ga3c::Ext ex;
+    std::memset(&ex, 0, sizeof(ex));
+    ex.value_kernel = val->value_kernel; ex.value_bias = val->value_bias; ex.value = val->value;
+    return ga3c_launch_ext(k, ex, stream);
+  }
   static thread_local bool lds_raised[16] = {false};
   int dev_id = 0;
   (void)hipGetDevice(&dev_id);
   hipError_t e = hipSuccess;
   if (!lds_raised[dev_id & 15]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ga3c::ga3c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ga3c::ga3c_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             static_cast<int>(GA3C_LDS));
     if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: hipFuncSetAttribute: %s", hipGetErrorString(e));
     lds_raised[dev_id & 15] = true;
@@ -2651,11 +2735,12 @@ int cagpu_ga3c(const CaParams* p, const CaState* s, const float* obs, const CaNe
   // the tile height (64 / 48 / 32 rows) is chosen on the device from the number of live rows: the grid covers the worst
   // case (32-row tiles); workgroups beyond the last tile leave at once
   const unsigned grid = static_cast<unsigned>((k.B + 31) / 32);
-  hipLaunchKernelGGL(ga3c::ga3c_kernel, dim3(grid), dim3(ga3c::NT), GA3C_LDS, static_cast<hipStream_t>(stream), k);
+  hipLaunchKernelGGL(ga3c::ga3c_kernel<false>, dim3(grid), dim3(ga3c::NT), GA3C_LDS, static_cast<hipStream_t>(stream), k, ga3c::NoExt{});
   e = hipGetLastError();
   if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
   return CA_OK;
 }
+}  // namespace
 
 static int generate_impl(int64_t num_cases, int32_t num_agents, int32_t n_min, int32_t n_max, const double* side_ranges,
                          int32_t n_ranges, double side_lo, double side_hi, double speed_lo, double speed_hi, double radius_lo,

@@ -77,6 +77,16 @@ struct Args {
   int N, K, obs_clip, sort_mode, ragged;
   double sensing_horizon;
 };
+// What cagpu_ga3c_query / cagpu_ga3c_value add (ga3c_kernel<true> only; the default launch carries none of it).
+//   query: the rows are ALL B rows of the plain array Args.obs [B, W - 1] -- the policy vector X itself (no is_learning column
+//   ahead of it: Args.W stays "X's width + 1"), no flag words, no packed list; value_kernel / value_bias: logits_v, the
+//   twelfth column of the padded logits block (nullptr: the column stays zero); value [B], action [B]: nullable outputs.
+struct Ext {
+  const float *value_kernel, *value_bias;
+  float* value;
+  int32_t* action;
+  int query;
+};
 
 // Who needs an action: GA3C-CADRL agents that are not done (collision_avoidance_env.py:310-312)
 __device__ __forceinline__ bool needs_action(uint32_t f) {
@@ -485,7 +495,12 @@ __global__ void pack_kernel(const float* __restrict__ w, const int row0, const i
   for (int pl = 0; pl < NPL; ++pl) out[((kb * 16 + cb) * NPL + pl) * 64 + lane] = s.p[pl];
 }
 
-__global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g) {
+// The whole network for one tile.  EXT = false is the default launch (cagpu_ga3c); EXT = true adds the query row source,
+// the value column and the value / action outputs (cagpu_ga3c_query, cagpu_ga3c_value) -- every addition sits behind
+// `if constexpr (EXT)`: the default instantiation contains none of it (its second argument is the empty NoExt).
+struct NoExt {};
+template <bool EXT>
+__global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typename std::conditional<EXT, Ext, NoExt>::type ex) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* hostv = reinterpret_cast<float*>(smem);          // [TM][4]  normalised dist_to_goal, heading, pref_speed, radius
   int* seqv = reinterpret_cast<int*>(hostv + TM * 4);     // [TM]     sequence_length
@@ -509,6 +524,8 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g) {
 
   // ---- the tile's rows: slot t holds packed row rows[row0 + t] (or row row0 + t itself without the packed list)
   if (row0 >= n_rows) return;  // workgroup-uniform (the grid covers the worst case: every row alive, 32-row tiles)
+  bool plain = false;
+  if constexpr (EXT) plain = ex.query != 0;  // query rows: every row of a plain array of policy vectors
   auto row_of = [&](const int slot) -> long {
     const long t = row0 + slot;
     return (slot < tm && t < n_rows) ? (g.rows ? static_cast<long>(g.rows[t]) : t) : -1;
@@ -516,7 +533,7 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g) {
   bool need = false;
   if (tid < TM) {
     const long i = row_of(tid);
-    need = i >= 0 && (g.rows != nullptr ||
+    need = i >= 0 && (g.rows != nullptr || plain ||
                       (needs_action(g.flags[i]) && (!g.net.agent_net || g.net.agent_net[i] == g.net.net_index)));
   }
   if (!__syncthreads_or(need ? 1 : 0)) return;
@@ -664,7 +681,7 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g) {
     const int rr = tid >> 2, c0 = (tid & 3) * PER;
     const long i = row_of(rr);
     const bool row_ok = i >= 0;
-    const float* orow = g.obs + (row_ok ? i : 0) * g.W + 1;
+    const float* orow = g.obs + (row_ok ? i : 0) * (plain ? g.W - 1 : g.W) + (plain ? 0 : 1);  // (a query row IS obs[1:])
     // input_mean / input_std through LDS: 276 loads per workgroup instead of 70 per thread (105 vector-memory instructions per
     // thread stalled on the 63 a wave may have in flight; the table sits in the union's slack behind the LSTM's share)
     static_assert(UNION_FLOATS - LSTM_FLOATS >= 2 * XIN && XIN <= NT, "room for the table");
@@ -678,7 +695,7 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g) {
     for (int j = 0; j < PER; ++j) {
       const int c = c0 + j;
       const int cc = c < XIN ? c : XIN - 1;
-      const int co = (cc + 1 < g.W) ? cc : g.W - 2;  // W >= 6
+      const int co = (cc + 1 < g.W) ? cc : g.W - 2;  // W >= 6 (a query: W >= 2)
       xv[j] = orow[co];
     }
     GTICK(14);  // (ablate builds: kernel start -> every load issued; GTICK(15): -> the barrier passed; GTICK(0): the rest)
@@ -949,18 +966,29 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g) {
   __syncthreads();
 
   GTICK(5);
-  // ---- logits_p: 11 columns = one (padded) column block; wave w takes row block w
+  // ---- logits_p: 11 columns = one (padded) column block; wave w takes row block w.  EXT: column 11 of the block is
+  // logits_v (the value head, `Squeeze` of the graph) on the same exact-f32 MFMA; the columns do not see each other.
   if (wv < nrb) {  // (wave-uniform)
     f32x4 lacc = f32x4{0.f, 0.f, 0.f, 0.f};
     const float* ap = act + (wv * 16 + m) * ACT_LD + q * 64;
     // all 64 weights of this lane first (clamped column + select: no branch, one memory latency), then the MFMAs
     const int mc = m < 11 ? m : 0;
-    const float keep = m < 11 ? 1.f : 0.f;
+    float keep = m < 11 ? 1.f : 0.f;
     const float* wp = g.net.logits_kernel + (q * 64) * 11 + mc;
+    const float* bp = g.net.logits_bias + mc;
+    int ws = 11;
+    if constexpr (EXT) {
+      if (m == 11 && ex.value_kernel) {  // logits_v/kernel [256, 1], bias [1]
+        wp = ex.value_kernel + q * 64;
+        bp = ex.value_bias;
+        ws = 1;
+        keep = 1.f;
+      }
+    }
     float lw[64];
 #pragma unroll
-    for (int kk = 0; kk < 64; ++kk) lw[kk] = wp[kk * 11];
-    const float bb = g.net.logits_bias[mc] * keep;
+    for (int kk = 0; kk < 64; ++kk) lw[kk] = wp[kk * ws];
+    const float bb = *bp * keep;
 #pragma unroll
     for (int kk = 0; kk < 64; kk += 4) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(ap + kk);
@@ -987,8 +1015,17 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g) {
         bv = l[c];
         best = c;
       }
-    g.ext[2 * i] = static_cast<double>(best);
-    g.ext[2 * i + 1] = 0.0;
+    if constexpr (EXT) {
+      if (g.ext) {
+        g.ext[2 * i] = static_cast<double>(best);
+        g.ext[2 * i + 1] = 0.0;
+      }
+      if (ex.action) ex.action[i] = best;
+      if (ex.value) ex.value[i] = l[11];
+    } else {
+      g.ext[2 * i] = static_cast<double>(best);
+      g.ext[2 * i + 1] = 0.0;
+    }
     if (g.logits)
       for (int c = 0; c < 11; ++c) g.logits[i * 11 + c] = l[c];
   }

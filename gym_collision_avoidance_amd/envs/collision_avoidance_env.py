@@ -88,6 +88,9 @@ class CollisionAvoidanceEnv(Env):
         self.zero_copy = bool(zero_copy)
         self.lookahead = (0 if zero_copy else None) if lookahead is None else max(0, int(lookahead))
         self._la_on, self._la_dt_ok = False, True
+        # GA3C-CADRL: also evaluate the network's value head with every policy query (set before reset();
+        # core.BatchedSim.ga3c_value [E, N], GA3CCADRLPolicy.find_next_action_and_value)
+        self.keep_ga3c_value = False
         self._initialize_rewards()
         self.num_agents = Config.MAX_NUM_AGENTS_IN_ENVIRONMENT
         self.dt_nominal = Config.DT
@@ -531,11 +534,15 @@ class CollisionAvoidanceEnv(Env):
             if None in paths:
                 raise RuntimeError("a GA3CCADRLPolicy agent was not initialised: call agent.policy.initialize_network()")
             order = sorted(paths)
-            if getattr(sim, "_net_paths", None) != order:
+            for n in nets:   # the host-callable query of these policy objects runs where the env runs
+                n.device = n.nn.device = str(sim.device)
+            keep_v = bool(self.keep_ga3c_value)
+            if getattr(sim, "_net_paths", None) != order or keep_v != (sim.ga3c_value is not None):
                 sim._nets.clear()
                 sim._net = None
+                sim.ga3c_value = None
                 for idx, path in enumerate(order):
-                    sim.load_ga3c(next(n.weights for n in nets if n.weights_path == path), index=idx)
+                    sim.load_ga3c(next(n.weights for n in nets if n.weights_path == path), index=idx, keep_value=keep_v)
                 sim._net_paths = order
             if len(order) > 1:
                 # agents of one batch on different checkpoints (every agent owns its policy object and session in the

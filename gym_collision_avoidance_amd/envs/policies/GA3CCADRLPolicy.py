@@ -1,5 +1,7 @@
 import os
 
+import numpy as np
+
 from gym_collision_avoidance_amd import _native as nat
 from gym_collision_avoidance_amd.envs.policies.GA3C_CADRL import network
 from .InternalPolicy import InternalPolicy
@@ -19,19 +21,69 @@ class GA3CCADRLPolicy(InternalPolicy):
     def __init__(self):
         InternalPolicy.__init__(self, str="GA3C_CADRL")
         self.possible_actions = network.Actions()
+        self.device = "cuda:0"   # where the host-callable query runs: initialize_network(device=...), or the env's own device
+        self.nn = network.NetworkVP_rnn(self.device, "network", self.possible_actions.num_actions)
         self.weights = None
         self.weights_path = None
 
     def initialize_network(self, **kwargs):
         """kwargs['checkpt_name'] (default 'network_01900000'), kwargs['checkpt_dir'] (default 'IROS18'; relative =
         one of the shipped conversions under data/ga3c_cadrl/, absolute = a directory holding <name>.npz or the
-        reference's TensorFlow checkpoint files <name>.index / .data-00000-of-00001) -- GA3CCADRLPolicy.py:23-47."""
+        reference's TensorFlow checkpoint files <name>.index / .data-00000-of-00001) -- GA3CCADRLPolicy.py:23-47.
+        kwargs['device'] (optional): the GPU find_next_action() queries on; an env that takes the agent sets it to its own."""
+        if kwargs.get("device") is not None:
+            self.device = self.nn.device = str(kwargs["device"])
         name = kwargs.get("checkpt_name", "network_01900000")
         d = kwargs.get("checkpt_dir", "IROS18")
         if not os.path.isabs(d):
             d = os.path.join(network.DATA_DIR, d)
         self.weights_path = os.path.join(d, name)
-        self.weights = network.load_weights(self.weights_path)
+        self.nn.simple_load(self.weights_path)
+        self.weights = self.nn.weights
+
+    @staticmethod
+    def policy_vector(obs):
+        """the observation dict -> the [1, W - 1] vector the network reads: the states of Config.STATES_IN_OBS that are not
+        in Config.STATES_NOT_USED_IN_POLICY, flattened, in order (GA3CCADRLPolicy.py:68-74); an array is taken as that
+        vector itself (pref_speed is its column 3)"""
+        from gym_collision_avoidance_amd.envs import Config
+        if isinstance(obs, dict):
+            parts = [np.asarray(obs[s], dtype=np.float64).flatten() for s in Config.STATES_IN_OBS
+                     if s not in Config.STATES_NOT_USED_IN_POLICY]
+            vec = np.hstack(parts) if parts else np.array([])
+        else:
+            vec = np.asarray(obs, dtype=np.float64).reshape(-1)
+        return np.expand_dims(vec, axis=0)
+
+    def _query(self, obs, want):
+        if self.weights is None:
+            raise RuntimeError("GA3CCADRLPolicy: the network is not loaded, call initialize_network() first")
+        from gym_collision_avoidance_amd import core
+        vec = self.policy_vector(obs)
+        if vec.shape[1] < 4:
+            raise ValueError("GA3CCADRLPolicy: the policy vector needs at least num_other_agents, dist_to_goal, "
+                             "heading_ego_frame and pref_speed, got %d columns" % vec.shape[1])
+        r = core.ga3c_query(vec.astype(np.float32), self.weights, want=want, device=self.nn_device())
+        pref_speed = float(np.asarray(obs["pref_speed"]).reshape(-1)[0]) if isinstance(obs, dict) else float(vec[0, 3])
+        return pref_speed, {k: v.cpu().numpy() for k, v in r.items()}
+
+    def nn_device(self):
+        return network._torch_device(self.device)
+
+    def _action(self, pref_speed, index):
+        raw = self.possible_actions.actions[int(index)]
+        return np.array([pref_speed * raw[0], raw[1]])
 
     def find_next_action(self, obs, agents, i):
-        raise RuntimeError("GA3CCADRLPolicy runs on the device (cagpu_ga3c); it has no per-agent host implementation")
+        """The reference's per-agent call (GA3CCADRLPolicy.py:49-84) on the device's query kernel: obs is THIS agent's
+        observation dict (or the policy vector itself as an array); `agents` and `i` are unused, as there.  One one-row launch (cagpu_ga3c_query) -- the batched
+        simulator does not come through here, it evaluates every agent of every env in one launch of the same code.
+        Returns [pref_speed * a0, a1]."""
+        pref_speed, r = self._query(obs, ("action",))
+        return self._action(pref_speed, r["action"][0])
+
+    def find_next_action_and_value(self, obs, agents, i):
+        """find_next_action and the network's value of the state (`Squeeze:0`), from one launch -> (action, value);
+        name and shape as CADRLPolicy.find_next_action_and_value (CADRLPolicy.py:43-48)."""
+        pref_speed, r = self._query(obs, ("action", "value"))
+        return self._action(pref_speed, r["action"][0]), float(r["value"][0])

@@ -8,6 +8,8 @@ matrix-core kernel of csrc/cagpu_ga3c.inc and this module only gets its weights 
   * `read_checkpoint(p)`    -- reads a TF "V2" checkpoint (`p.index` + `p.data-00000-of-00001`) without TensorFlow, so the
                                reference's own checkpoint directories keep working;
   * `load_weights(p)`       -- `p.npz` (the shipped conversions under data/ga3c_cadrl/) or a TF checkpoint prefix.
+  * `NetworkVPCore` / `NetworkVP_rnn` -- the reference's network object: `predict_p`, `predict_v`, `predict_p_and_v` on
+                               arrays of policy vectors, evaluated by the batched query kernel (`cagpu_ga3c_query`).
 """
 import os
 import struct
@@ -164,3 +166,86 @@ def _load_weights(path):
     if os.path.exists(path + ".index"):
         return read_checkpoint(path)
     raise FileNotFoundError("no GA3C-CADRL weights at %s(.npz|.index)" % path)
+
+
+# ---------------------------------------------------------------- the network object (network.py:18-78)
+def _torch_device(device):
+    """the reference passes TensorFlow device names ('/cpu:0', '/gpu:1'); the network here runs on a GPU only:
+    '/gpu:N' -> 'cuda:N', a torch device / 'cuda:N' as it is, anything else (None, '/cpu:0') -> 'cuda:0'"""
+    if device is None:
+        return "cuda:0"
+    d = str(device)
+    if d.startswith("cuda"):
+        return d
+    if d.lower().startswith("/gpu:"):
+        return "cuda:" + d[5:]
+    return "cuda:0"
+
+
+class NetworkVPCore(object):
+    """The reference's network object (network.py:18-74) on the batched query kernel (core.ga3c_query ->
+    cagpu_ga3c_query): `predict_p(x)` for a [B, width] array of policy vectors X = obs[1:] returns the [B, 11] softmax,
+    `predict_v(x)` the [B] value (`Squeeze:0`), `predict_p_and_v(x)` both from ONE launch.  Inputs: numpy or torch; results:
+    numpy float32, or device tensors with as_tensor=True (no host copy).  There is no session: `simple_load` only
+    resolves and caches the weights; the device copy is made at the first query and cached per checkpoint."""
+
+    def __init__(self, device, model_name, num_actions):
+        self.device = device
+        self.model_name = model_name
+        self.num_actions = num_actions
+        self.weights = None
+
+    def simple_load(self, filename=None):
+        """filename: what load_weights accepts -- '<prefix>' or '<prefix>.npz' of a converted checkpoint, or the prefix
+        of the reference's TensorFlow checkpoint files (network.py:43-74)."""
+        if filename is None:
+            raise NotImplementedError("[network.py] simple_load needs a checkpoint file name")
+        self.weights = load_weights(filename)
+
+    def crop_x(self, x):
+        """[B, width] -> [B, 138]: wider rows are cut, narrower ones zero-padded (network.py:24-35).  The kernel does
+        the same on its own; this is the host-side statement of it (numpy in, numpy out; torch in, torch out)."""
+        w = x.shape[-1]
+        if w > INPUT_LENGTH:
+            return x[:, :INPUT_LENGTH]
+        if w < INPUT_LENGTH:
+            if hasattr(x, "new_zeros"):
+                x_ = x.new_zeros((x.shape[0], INPUT_LENGTH))
+            else:
+                x_ = np.zeros((x.shape[0], INPUT_LENGTH), dtype=np.asarray(x).dtype)
+            x_[:, :w] = x
+            return x_
+        return x
+
+    def _query(self, x, want):
+        if self.weights is None:
+            raise RuntimeError("NetworkVPCore: no weights loaded, call simple_load(filename) first")
+        from gym_collision_avoidance_amd import core
+        import torch
+        dev = x.device if (torch.is_tensor(x) and x.is_cuda) else _torch_device(self.device)
+        if not torch.is_tensor(x):
+            x = np.asarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        return core.ga3c_query(x, self.weights, want=want, device=dev)
+
+    @staticmethod
+    def _out(t, as_tensor):
+        return t if as_tensor else t.cpu().numpy()
+
+    def predict_p(self, x, as_tensor=False):
+        import torch
+        return self._out(torch.softmax(self._query(x, ("logits",))["logits"], dim=1), as_tensor)
+
+    def predict_v(self, x, as_tensor=False):
+        return self._out(self._query(x, ("value",))["value"], as_tensor)
+
+    def predict_p_and_v(self, x, as_tensor=False):
+        import torch
+        r = self._query(x, ("logits", "value"))
+        return self._out(torch.softmax(r["logits"], dim=1), as_tensor), self._out(r["value"], as_tensor)
+
+
+class NetworkVP_rnn(NetworkVPCore):
+    def __init__(self, device, model_name, num_actions):
+        super(NetworkVP_rnn, self).__init__(device, model_name, num_actions)

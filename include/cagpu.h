@@ -522,6 +522,40 @@ uint64_t cagpu_render_work_bytes(int32_t num_frames, int32_t num_agents, int32_t
 int cagpu_ga3c(const CaParams *p, const CaState *s, const float *obs, const CaNet *net, double *ext_actions,
                float *logits, void *stream);
 
+/* Replaces: NetworkVPCore.predict_p / crop_x (GA3C_CADRL/network.py:24-41) and the value fetch `Squeeze:0`
+ * (network.py:74, NetworkVP_rnn: logits_v) for ALL `rows` rows of a plain device array x [rows, width] of policy vectors
+ * X = obs[1:] (num_other_agents, dist_to_goal, heading_ego_frame, pref_speed, radius, 19 x 7): no simulator, no flag
+ * words.  width as crop_x: columns beyond 138 are ignored, missing ones are raw zeros before the normalisation; the
+ * sequence length is int(x[:,0]) clamped to 0..19.  Outputs, each nullable (not all): logits [rows,11] (logits_p before
+ * the softmax), value [rows] (needs value_kernel / value_bias = logits_v/{kernel [256,1], bias [1]}, device float32),
+ * action int32 [rows] (first maximum of the logits, like np.argmax).  The same kernel code and arithmetic as cagpu_ga3c
+ * (a row's results are bit-identical to the simulator path's on the same observation); the value is the twelfth column
+ * of the padded logits block on the exact f32 MFMA.  rows == 0: CA_OK, nothing launched.  rows >= 2^31:
+ * CA_EUNSUPPORTED.  net->rows_scratch / agent_net are not used.  The fp16-range guard (cagpu_device_faults bit 1)
+ * applies.  cagpu_last_kernel() names the launch "ga3c_kernel<true> query ...". */
+typedef struct CaNetQuery {
+  const float *x;                          /* device float32 [rows, width], row-major */
+  int64_t rows;
+  int32_t width, reserved0;
+  const float *value_kernel, *value_bias;  /* logits_v; both NULL: no value */
+  float *logits;                           /* [rows, 11] or NULL */
+  float *value;                            /* [rows] or NULL */
+  int32_t *action;                         /* [rows] or NULL */
+} CaNetQuery;
+int cagpu_ga3c_query(const CaNet *net, const CaNetQuery *q, void *stream);
+
+/* cagpu_ga3c with the value head: value [E,N] (device float32) is written for exactly the agents cagpu_ga3c evaluates
+ * (live GA3C-CADRL agents, of this checkpoint with CaNet.agent_net), every other entry is left alone.  Replaces: the
+ * `Squeeze:0` fetch of the reference's find_next_action_and_value-style callers (network.py:74) for those agents.
+ * v == NULL: exactly cagpu_ga3c (the same launch).  All three members of v are required.  ext_actions and logits are
+ * bit-identical to cagpu_ga3c's.  cagpu_last_kernel() names the launch "ga3c_kernel<true> sim ...". */
+typedef struct CaNetValue {
+  const float *value_kernel, *value_bias;  /* logits_v/{kernel [256,1], bias [1]} */
+  float *value;                            /* [E, N] */
+} CaNetValue;
+int cagpu_ga3c_value(const CaParams *p, const CaState *s, const float *obs, const CaNet *net, double *ext_actions,
+                     float *logits, const CaNetValue *v, void *stream);
+
 /* The size of CaNet.packed, and the one-time split of a checkpoint's weights into it: reads net->lstm_kernel,
  * layer1_kernel, layer2_kernel, fc1_kernel (device float32, the checkpoint's [in, out] layout) and writes `bytes` =
  * cagpu_ga3c_packed_bytes() bytes at `packed` (device, 16-byte aligned); the LSTM kernel's columns are stored multiplied (in
