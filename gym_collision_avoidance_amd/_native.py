@@ -92,6 +92,14 @@ class CaStepEx(C.Structure):
                 ("traj", _P), ("fin", _P), ("log", _P)]
 
 
+class CaPolicyDraw(C.Structure):
+    """the policy lottery of an auto-reset (cagpu_step_draw / cagpu_policy_draw); include/cagpu.h states the rule"""
+    _fields_ = [("cdf", _P), ("policy_bits", _P), ("num_policies", C.c_int32), ("ensure", C.c_int32), ("seed", C.c_uint64)]
+
+
+POLICY_DRAW_BITS = 0xFC0   # the bits of a flag word a draw rewrites: IS_LEARNING, STILL_LEARNING, the policy id
+
+
 class CaRender(C.Structure):
     _fields_ = [("out", _P), ("num_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("flags", C.c_int32),
                 ("xmin", C.c_double), ("ymax", C.c_double), ("s16", C.c_double), ("frame_env", _P), ("frame_col", _P),
@@ -124,7 +132,7 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_ga3c_packed_bytes", "cagpu_ga3c_pack", "cagpu_rollout_ring", "cagpu_ring_snapshots", "cagpu_debug_copy8", "cagpu_device_faults_async",
            "cagpu_step_maps", "cagpu_laserscan_maps", "cagpu_occupancy_grid", "cagpu_occupancy_grid_maps",
            "cagpu_step_traj", "cagpu_rollout_traj", "cagpu_step_final", "cagpu_rollout_final",
-           "cagpu_step_log", "cagpu_rollout_log", "cagpu_step_ex",
+           "cagpu_step_log", "cagpu_rollout_log", "cagpu_step_ex", "cagpu_step_draw", "cagpu_policy_draw",
            "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes", "cagpu_ga3c_query", "cagpu_ga3c_value")
 
 _lib = None
@@ -173,6 +181,8 @@ def lib():
     L.cagpu_rollout_log.argtypes = [PP, PS, PO, _P, PA, C.c_int32, C.c_int32, C.c_int64, C.POINTER(CaTraj),
                                     C.POINTER(CaFinal), C.POINTER(CaEpLog), _P]
     L.cagpu_step_ex.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaStepEx), _P]
+    L.cagpu_step_draw.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaStepEx), C.POINTER(CaPolicyDraw), _P]
+    L.cagpu_policy_draw.argtypes = [PP, PS, PO, PA, C.POINTER(CaPolicyDraw), _P, _P]
     L.cagpu_render.argtypes = [PP, PS, C.POINTER(CaMap), C.POINTER(CaRender), _P]
     L.cagpu_render_maps.argtypes = [PP, PS, C.POINTER(CaMapSet), C.POINTER(CaRender), _P]
     L.cagpu_render_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

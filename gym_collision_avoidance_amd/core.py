@@ -58,6 +58,15 @@ GA3C_DEFAULT_WEIGHTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # (see BatchedSim._stream_handle)
 
 
+def policy_word_bits(policy, is_learning=None, still_learning=None):
+    """bits 6..11 of a flag word for a policy id (CA_POL_*): one entry of a policy draw's pool (set_policy_draw).  The
+    learning bits default to what set_plugins gives the policy."""
+    learn = policy in (nat.POL_LEARNING, nat.POL_LEARNING_GA3C)
+    isl = learn if is_learning is None else bool(is_learning)
+    stl = learn if still_learning is None else bool(still_learning)
+    return (int(policy) << nat.POLICY_SHIFT) | (nat.IS_LEARNING if isl else 0) | (nat.STILL_LEARNING if stl else 0)
+
+
 class BatchedSim(object):
     PROBE_EVERY = 8   # the device's fault word is probed behind every 8th ring refill (and every 256th single launch)
 
@@ -127,6 +136,9 @@ class BatchedSim(object):
         # The references below are made once: p, _cs, _co and _sx are never replaced; _ar is, by set_fixture_table only,
         # which re-makes _ar_ref.
         self._step_ex = self.lib.cagpu_step_ex
+        # ... except while a policy draw is on (set_policy_draw): _launch is then cagpu_step_draw with the draw bound in
+        self._launch = self._step_ex
+        self._draw = None         # the policy draw: dict(c=CaPolicyDraw, cdf, bits, has_ga3c) / None
         self._sx = nat.CaStepEx(n_steps=1)
         self._p_ref, self._cs_ref, self._co_ref, self._sx_ref = C.byref(self.p), C.byref(self._cs), C.byref(self._co), C.byref(self._sx)
         self._ar_ref = None
@@ -149,7 +161,8 @@ class BatchedSim(object):
         self._net_tensors = None
         self._nets = {}
         self._agent_net = None    # int32 [E, N]: which checkpoint an agent runs (set_ga3c_assignment)
-        self._has_ga3c = False    # some agent's policy is CA_POL_GA3C_CADRL (set_plugins)
+        self._has_ga3c = False    # some agent's policy is CA_POL_GA3C_CADRL (set_plugins), or may become it (set_policy_draw)
+        self._plugins_ga3c = False
         self._ga3c_ext = None
         self.ga3c_logits = None
         self.ga3c_value = None    # float32 [E, N] (load_ga3c(keep_value=True)): logits_v of the agents ga3c() evaluated
@@ -323,7 +336,8 @@ class BatchedSim(object):
                (stl * nat.STILL_LEARNING)
         cur = self._state["flags"]
         cur.copy_((cur & (0x3F | nat.ABSENT)) | torch.as_tensor(bits.astype(np.int32), device=self.device))
-        self._has_ga3c = bool((pol == nat.POL_GA3C_CADRL).any())
+        self._plugins_ga3c = bool((pol == nat.POL_GA3C_CADRL).any())
+        self._has_ga3c = self._plugins_ga3c or (self._draw is not None and self._draw["has_ga3c"])
 
     def ga3c_rows(self):
         """number of agents the last ga3c() call evaluated (device -> host read: synchronises)"""
@@ -473,6 +487,8 @@ class BatchedSim(object):
             self._la["prep"] = None
         if table is None:
             self._ar, self._ar_ref, self._table = None, None, None
+            if self._draw is not None:  # (no auto-reset, nothing is ever drawn: the policy draw goes with the table)
+                self.set_policy_draw(None)
             if self._fin_on:        # (no auto-reset, nothing is overwritten: the final record goes with the table)
                 self.keep_final(False)
             if self._log is not None:   # (... and no episode is ever logged)
@@ -500,6 +516,73 @@ class BatchedSim(object):
                                    reset_plan=None if self._reset_plan is None else self._reset_plan.data_ptr(),
                                    heading_seed=int(heading_seed) & 0xFFFFFFFFFFFFFFFF)
         self._ar_ref = C.byref(self._ar)
+        if self._draw is not None and self._draw["c"].seed == self._ar.heading_seed:
+            raise ValueError("heading_seed equals the policy draw's seed: an agent's heading and policy would be the same uniform")
+
+    def set_policy_draw(self, pool_bits, distr=None, ensure=None, seed=0x706F6C69637931):
+        """Draw every agent's policy anew at each auto-reset, on the device (include/cagpu.h CaPolicyDraw) -- the batched
+        form of test_cases.py cadrl_test_case_to_agents: np.random.choice(policies, num_agents, p=policy_distr), then
+        `policy_to_ensure` written over one random agent if nobody drew it.  Needs a fixture table.
+          pool_bits: per pool entry, bits 6..11 of the flag word (policy_word_bits(): IS_LEARNING, STILL_LEARNING, policy id);
+          distr:     the pool's probabilities (normalised as np.random.choice does: cumsum / its last element);
+          ensure:    None, or the pool index every episode must hold;
+          seed:      the Philox key, != 0 and != the table's heading_seed.
+        pool_bits None: off.  While it is on, step(), rollout(), the look-ahead ring and the replay of a rewind launch
+        through cagpu_step_draw -- the draw is a pure function of (seed, global env id, episode number), so all of them
+        and every shard layout produce the same flag words -- and reset() / reset_from_table() run cagpu_policy_draw for
+        the envs they touch.  A host reset zeroes reset_count, so those envs REPLAY the policy sequence of their first
+        episodes (as they replay their cases and headings); pass a new seed for a new sequence.  Dynamics bits are never
+        drawn.  An env that auto-reset starts without a pipelined plan (queried on its pre-move state: bit-identical)."""
+        self.sync()
+        if self._la is not None:
+            self._la["prep"] = None
+        if pool_bits is None:
+            self._draw, self._launch = None, self._step_ex
+            self._has_ga3c = self._plugins_ga3c
+            return
+        if self._ar is None:
+            raise ValueError("set_policy_draw needs a fixture table (set_fixture_table): policies are drawn at auto-resets")
+        bits = np.asarray(pool_bits, np.int64).reshape(-1)
+        P = bits.size
+        prob = np.asarray(distr, np.float64).reshape(-1)
+        if not 1 <= P <= 8 or prob.size != P:
+            raise ValueError("the pool needs 1..8 entries and one probability per entry")
+        if (prob < 0).any() or not prob.sum() > 0:
+            raise ValueError("policy_distr must be non-negative with a positive sum")
+        if (bits & ~nat.POLICY_DRAW_BITS).any():
+            raise ValueError("pool_bits may only hold bits 6..11 (IS_LEARNING, STILL_LEARNING, the policy id)")
+        ens = -1 if ensure is None else int(ensure)
+        if not -1 <= ens < P:
+            raise ValueError("ensure must be None or a pool index")
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if seed == 0 or seed == self._ar.heading_seed:
+            raise ValueError("the policy draw's seed must be != 0 and != the table's heading_seed")
+        cdf = prob.cumsum()
+        cdf /= cdf[-1]
+        t_cdf = torch.as_tensor(cdf, dtype=torch.float64).to(self.device)
+        t_bits = torch.as_tensor(bits.astype(np.int32)).to(self.device)
+        d = nat.CaPolicyDraw(cdf=t_cdf.data_ptr(), policy_bits=t_bits.data_ptr(), num_policies=P, ensure=ens, seed=seed)
+        has_ga3c = bool((((bits >> nat.POLICY_SHIFT) & 0xF) == nat.POL_GA3C_CADRL).any())
+        self._draw = dict(c=d, ref=C.byref(d), cdf=t_cdf, bits=t_bits, has_ga3c=has_ga3c)
+        draw_ref, step_draw = self._draw["ref"], self.lib.cagpu_step_draw
+        self._launch = lambda p, s, o, ext, ar, sx, stream: step_draw(p, s, o, ext, ar, sx, draw_ref, stream)
+        # (any slot may become a GA3C-CADRL agent at an auto-reset: the network then runs before every step)
+        self._has_ga3c = self._plugins_ga3c or has_ga3c
+
+    def _policy_draw_now(self, mask=None):
+        """cagpu_policy_draw: the lottery of the episode every (masked) env is in, on the state and column 0 of `obs`"""
+        nat.check(self.lib.cagpu_policy_draw(self._p_ref, self._cs_ref, self._co_ref, self._ar_ref, self._draw["ref"],
+                                             None if mask is None else mask.data_ptr(), self._stream()))
+
+    def policy_ids(self):
+        """int32 [E, N]: the policy id (CA_POL_*) every agent slot runs in the step last handed out (through sync())"""
+        return (self.state["flags"] >> nat.POLICY_SHIFT) & 0xF
+
+    def learning_mask(self, still_learning=False):
+        """bool [E, N]: CA_IS_LEARNING (still_learning: CA_STILL_LEARNING) of every agent slot that holds an agent (an
+        absent slot of a ragged batch keeps the word of its last agent: False here), through sync()"""
+        flags = self.state["flags"]
+        return ((flags & (nat.STILL_LEARNING if still_learning else nat.IS_LEARNING)) != 0) & ((flags & nat.ABSENT) == 0)
 
     # ---------------------------------------------------------------- the C-ABI calls
     def reset(self, cases, headings=None, mask=None):
@@ -514,6 +597,8 @@ class BatchedSim(object):
         nat.check(self.lib.cagpu_reset(C.byref(self.p), C.byref(self._cs), C.byref(self._co), c.data_ptr(),
                                        None if h is None else h.data_ptr(), None if m is None else m.data_ptr(),
                                        self._stream()))
+        if self._draw is not None:   # episode 0 of the envs this reset touches needs its lottery too
+            self._policy_draw_now(m)
         self._keep = [c, h, m]  # keep alive until the stream has consumed them
         if self._log is not None:   # the reset envs count their episodes from 0 again: undrained records of theirs are discarded
             episodes.clear(self._log["head"], self._log["cursor"], m)
@@ -707,7 +792,7 @@ class BatchedSim(object):
             ext = None if e is None else e.data_ptr()
         if self.fresh_outputs:
             self._new_outputs()
-        rc = self._step_ex(self._p_ref, self._cs_ref, self._co_ref, ext, self._ar_ref, self._sx_ref, self._stream_handle())
+        rc = self._launch(self._p_ref, self._cs_ref, self._co_ref, ext, self._ar_ref, self._sx_ref, self._stream_handle())
         if rc != 0:
             nat.check(rc)
         if fast:
@@ -736,7 +821,7 @@ class BatchedSim(object):
         # env's most recent terminal record of the launch -- and the log, every ending in its own slot
         chunk, ct = self._traj_chunk(int(n_steps)) if self._traj_on else (None, None)
         sx = nat.CaStepEx(n_steps=int(n_steps), traj=None if ct is None else C.addressof(ct), fin=self._sx.fin, log=self._sx.log)
-        nat.check(self._step_ex(self._p_ref, self._cs_ref, self._co_ref, None if e is None else e.data_ptr(), self._ar_ref,
+        nat.check(self._launch(self._p_ref, self._cs_ref, self._co_ref, None if e is None else e.data_ptr(), self._ar_ref,
                                 C.byref(sx), self._stream_handle()))
         if chunk is not None:
             self._traj_commit(chunk)
@@ -833,7 +918,7 @@ class BatchedSim(object):
         if rec:
             chunk, ct = self._traj_chunk(k, prep["traj"])
             prep["sx"].traj = C.addressof(ct)
-        rc = self._step_ex(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], prep["sx_ref"], self._stream_handle())
+        rc = self._launch(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], prep["sx_ref"], self._stream_handle())
         if rc != 0:
             nat.check(rc)
         if chunk is not None:
@@ -946,7 +1031,7 @@ class BatchedSim(object):
         if t < k:
             self._slab.copy_(la["snap"])
             if t > 0:              # (rewrites slot t - 1 with the values it already holds)
-                nat.check(self._step_ex(self._p_ref, self._cs_ref, self._co_ref, None, self._ar_ref,
+                nat.check(self._launch(self._p_ref, self._cs_ref, self._co_ref, None, self._ar_ref,
                                         C.byref(nat.CaStepEx(n_steps=t)), self._stream_handle()))
 
     # ---------------------------------------------------------------- the final record (include/cagpu.h CaFinal)

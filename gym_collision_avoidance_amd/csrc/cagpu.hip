@@ -99,6 +99,12 @@ struct KArgs {
   int32_t* log_head;
   int32_t log_cap;
   int32_t log_case_step;  // case_stride mod n_cases in [0, n_cases): the case an episode ran on from the next one's, no division
+  // policy draw (cagpu_step_draw; nullptr everywhere else): the members of CaPolicyDraw.  Appended: every older member keeps
+  // its kernarg offset
+  const double* draw_cdf;
+  const uint32_t* draw_bits;
+  unsigned long long draw_seed;
+  int32_t draw_n, draw_ensure;
 };
 
 // One agent's share of an episode-log record (CaEpLog): env e ends its episode number `ep` (its reset count before the
@@ -663,6 +669,74 @@ __device__ __forceinline__ int32_t map_draw(const unsigned long long seed, const
                                    0xFFFFFFFFu);
   const int m = static_cast<int>(floor(num_maps * u));
   return m < num_maps - 1 ? m : num_maps - 1;
+}
+
+// ---- policy draw (CaPolicyDraw in cagpu.h has the rule).  Its uniform for counter word `slot` of env ge's episode k:
+__device__ __forceinline__ double draw_uniform(const unsigned long long seed, const long ge, const int k, const unsigned slot) {
+  const unsigned long long g = static_cast<unsigned long long>(ge);
+  return gen::uniform_at(seed, static_cast<unsigned>(g), static_cast<unsigned>(g >> 32), static_cast<unsigned>(k), slot);
+}
+// step 1: #{j : cdf[j] <= u}, clamped to P - 1
+__device__ __forceinline__ int draw_index(const double* cdf, const int P, const double u) {
+  int j = 0;
+  for (int q = 0; q < P; ++q) j += static_cast<int>(cdf[q] <= u);
+  return j < P - 1 ? j : P - 1;
+}
+// step 2's slot: the r-th of n present slots takes `ensure`
+__device__ __forceinline__ int draw_ensure_rank(const unsigned long long seed, const long ge, const int k, const int n) {
+  const int r = static_cast<int>(floor(n * draw_uniform(seed, ge, k, 0xFFFFFFFEu)));
+  return r < n - 1 ? r : n - 1;
+}
+// The flag word of slot a of env ge in episode k.  The lane recomputes the draws of its env's other slots to settle the
+// ensure rule (N <= 64 here, a few times per episode): no exchange with another lane.  present(j): slot j holds an agent.
+template <typename Present>
+__device__ __forceinline__ uint32_t policy_draw_word(const double* cdf, const uint32_t* bits, const int P, const int ensure,
+                                                     const unsigned long long seed, const long ge, const int k, const int a,
+                                                     const int N, const Present present, const uint32_t flags) {
+  if (!present(a)) return flags;
+  int mine = draw_index(cdf, P, draw_uniform(seed, ge, k, static_cast<unsigned>(a)));
+  if (ensure >= 0 && mine != ensure) {
+    int n = 0, before = 0;
+    bool any = false;
+#pragma unroll 1
+    for (int j = 0; j < N; ++j) {
+      if (!present(j)) continue;
+      ++n;
+      before += static_cast<int>(j < a);
+      if (j != a && !any) any = draw_index(cdf, P, draw_uniform(seed, ge, k, static_cast<unsigned>(j))) == ensure;
+    }
+    if (!any && before == draw_ensure_rank(seed, ge, k, n)) mine = ensure;
+  }
+  return (flags & ~0xFC0u) | (bits[mine] & 0xFC0u);
+}
+
+// cagpu_policy_draw: the rule on the current state, one thread per agent slot
+struct DrawArgs {
+  uint32_t* flags;
+  const int32_t* reset_count;
+  float* obs;           // or nullptr
+  const uint8_t* mask;  // or nullptr
+  const double* cdf;
+  const uint32_t* bits;
+  unsigned long long seed;
+  long env_id_offset, total;
+  int32_t N, W, P, ensure, ragged;
+};
+__global__ __launch_bounds__(256) void policy_draw_kernel(const DrawArgs d) {
+  const long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= d.total) return;
+  const long e = i / d.N;
+  const int a = static_cast<int>(i - e * d.N);
+  if (d.mask && !d.mask[e]) return;
+  const uint32_t* fl = d.flags + e * d.N;
+  const bool ragged = d.ragged != 0;
+  const auto present = [&](const int j) { return !(ragged && (fl[j] & CA_ABSENT)); };
+  if (!present(a)) return;
+  // (the other slots' words are read for CA_ABSENT only, which no thread writes)
+  const uint32_t f = policy_draw_word(d.cdf, d.bits, d.P, d.ensure, d.seed, d.env_id_offset + e, d.reset_count[e], a, d.N,
+                                      present, fl[a]) & ~static_cast<uint32_t>(CA_PLAN_VALID);
+  d.flags[i] = f;
+  if (d.obs) d.obs[i * d.W] = (f & CA_IS_LEARNING) ? 1.f : 0.f;
 }
 
 // fixed: 7 f64 + 10 f32 + 4 u32 per agent slot (the 3 f64 of the episode scratch alias six ORCA float arrays) + the
@@ -1604,6 +1678,12 @@ LP1_UNROLL
               eplog_store(k.log_rows, k.log_head, k.log_cap, e, static_cast<int>(c), k.log_case_step, k.n_cases, N, a,
                           reset_cnt - 1, sh_r0[lane], sh_r1[lane], sh_r2[lane], r.flags, ep_step, any_coll, all_goal);
             reset_lane(r, k.table + (c * N + a) * 6, k.heading_seed != 0, h0, p);
+            if (k.draw_cdf) {  // policy draw (CaPolicyDraw; a uniform test): the new episode's policy bits of this slot
+              const double* rad = k.table + c * N * 6 + 5;
+              r.flags = policy_draw_word(k.draw_cdf, k.draw_bits, k.draw_n, k.draw_ensure, k.draw_seed, k.env_id_offset + e,
+                                         reset_cnt, a, N, [&](const int j) { return !p.ragged || rad[j * 6] > 0.0; }, r.flags);
+              if (RO) sh_flag[lane] = r.flags;  // (the copy of the reset observation takes is_learning from here)
+            }
             // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by its agent 0 lane
             if (!MULTI && k.map_seed && a == 0) k.env_map[e] = map_draw(k.map_seed, k.env_id_offset + e, reset_cnt, k.num_maps);
             ep_step = 0;
@@ -2048,9 +2128,11 @@ int launch_pipe2(const KArgs& k0, hipStream_t st) {
                 MULTI ? "true" : "false", grid, static_cast<size_t>(G::LDS), k.mode, k.yield_t > 0 ? " fair" : "",
                 k.traj_rows ? " traj" : "", k.fin_obs ? " final" : "");
   if (k.log_rows) std::strncat(g_last_kernel, " log", sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
+  if (k.draw_cdf) std::strncat(g_last_kernel, " draw", sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
   // (recording and the final record are template flags: the instantiations without them are the code they were before;
-  // the episode log rides on the FINAL instantiations behind a uniform test of its pointers -- no flag of its own)
-  if (k.fin_obs || k.log_rows) {
+  // the episode log and the policy draw ride on the FINAL instantiations behind uniform tests of their pointers -- no
+  // flags of their own)
+  if (k.fin_obs || k.log_rows || k.draw_cdf) {
     const bool fair = MULTI && k.yield_t > 0;
     if (k.traj_rows) {
       if (fair) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, MULTI, MULTI, true, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
@@ -2252,6 +2334,19 @@ static int check_map_set(const CaMapSet* set, const char* who) {
   return CA_OK;
 }
 
+// the argument checks of the policy draw (CaPolicyDraw), shared by cagpu_step_draw and cagpu_policy_draw
+static int check_draw(const CaPolicyDraw* d, const CaAutoReset* ar, const char* who) {
+  if (!d->cdf || !d->policy_bits) return fail(CA_EINVAL, "%s: NULL CaPolicyDraw.cdf or CaPolicyDraw.policy_bits", who);
+  if (d->num_policies < 1 || d->num_policies > 8) return fail(CA_EINVAL, "%s: CaPolicyDraw.num_policies must be in 1..8", who);
+  if (d->ensure < -1 || d->ensure >= d->num_policies)
+    return fail(CA_EINVAL, "%s: CaPolicyDraw.ensure must be -1 or a pool index below num_policies", who);
+  if (d->seed == 0) return fail(CA_EINVAL, "%s: CaPolicyDraw.seed must not be 0", who);
+  if (!ar) return fail(CA_EINVAL, "%s: a CaPolicyDraw without a CaAutoReset (no table: nothing is ever drawn)", who);
+  if (d->seed == ar->heading_seed)
+    return fail(CA_EINVAL, "%s: CaPolicyDraw.seed equals CaAutoReset.heading_seed (an agent's heading and policy would be the same uniform)", who);
+  return CA_OK;
+}
+
 // One step / rollout call as step_impl sees it: the CaStepEx fields plus what only the fixed entry points need.
 struct StepCall {
   int32_t n_steps = 1;
@@ -2262,6 +2357,7 @@ struct StepCall {
   const CaTraj* traj = nullptr;
   const CaFinal* fin = nullptr;
   const CaEpLog* log = nullptr;
+  const CaPolicyDraw* draw = nullptr;  // cagpu_step_draw
   // the record the entry point insists on (the older names: "traj may not be NULL" ...); cagpu_step_ex: none
   enum Need { NEED_NONE, NEED_SET, NEED_TRAJ, NEED_FIN, NEED_LOG } need = NEED_NONE;
   bool query_snapshot = false;   // cagpu_ring_snapshots: answer 1 / 0 instead of launching
@@ -2281,6 +2377,10 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
   if (c.need == StepCall::NEED_SET && !set) return fail(CA_EINVAL, "%s: NULL CaMapSet", c.who);
   if (c.map && set) return fail(CA_EINVAL, "%s: a CaMap and a CaMapSet at once", c.who);
   if (!c.ring && c.snapshot_delta != 0) return fail(CA_EINVAL, "%s: snapshot_delta without ring", c.who);
+  if (c.draw) {
+    const int rd = check_draw(c.draw, ar, c.who);
+    if (rd) return rd;
+  }
   if (want_log) {  // (first, like the final record's: a bad episode log is reported as such whatever else is wrong)
     if (!log || !log->rows || !log->head) return fail(CA_EINVAL, "cagpu: NULL CaEpLog, CaEpLog.rows or CaEpLog.head%s");
     if ((reinterpret_cast<uintptr_t>(log->rows) & 15u) || (reinterpret_cast<uintptr_t>(log->head) & 15u))
@@ -2330,6 +2430,11 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
     k.map_seed = ar ? set->map_seed : 0;  // (draws happen at auto-resets only)
   }
   k.n_steps = n_steps; k.mode = MODE_STEP;
+  if (c.draw) {
+    k.draw_cdf = c.draw->cdf; k.draw_bits = c.draw->policy_bits; k.draw_seed = c.draw->seed;
+    k.draw_n = c.draw->num_policies; k.draw_ensure = c.draw->ensure;
+    k.reset_plan = nullptr;  // (a plan belongs to the policy it was made for: a reset env is queried on its pre-move state)
+  }
   if (want_traj) { k.traj_rows = traj->rows; k.traj_ep = traj->episode; }
   if (want_fin) { k.fin_obs = fin->obs; k.fin_flags = fin->flags; }
   if (want_log) {
@@ -2372,6 +2477,41 @@ int cagpu_step_ex(const CaParams* p, const CaState* s, const CaOut* o, const dou
     c.map = x->map; c.set = x->set; c.traj = x->traj; c.fin = x->fin; c.log = x->log;
   }
   return step_impl(p, s, o, ext_actions, ar, c, stream);
+}
+
+int cagpu_step_draw(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
+                    const CaStepEx* x, const CaPolicyDraw* d, void* stream) {
+  if (!d) return cagpu_step_ex(p, s, o, ext_actions, ar, x, stream);
+  StepCall c;
+  c.who = "cagpu_step_draw";
+  if (x) {
+    c.n_steps = x->n_steps; c.ring = x->ring != 0; c.snapshot_delta = x->snapshot_delta;
+    c.map = x->map; c.set = x->set; c.traj = x->traj; c.fin = x->fin; c.log = x->log;
+  }
+  c.draw = d;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
+}
+
+int cagpu_policy_draw(const CaParams* p, const CaState* s, const CaOut* o, const CaAutoReset* ar, const CaPolicyDraw* d,
+                      const uint8_t* env_mask, void* stream) {
+  if (!p || !s || !d) return fail(CA_EINVAL, "cagpu_policy_draw: NULL argument%s");
+  const int rd = check_draw(d, ar, "cagpu_policy_draw");
+  if (rd) return rd;
+  if (p->num_envs < 1 || p->num_agents < 1 || p->num_agents > big::NT_MAX || p->max_obs < 0)
+    return fail(CA_EINVAL, "cagpu_policy_draw: bad sizes%s");
+  if (!s->flags || !s->reset_count) return fail(CA_EINVAL, "cagpu_policy_draw: NULL state pointer%s");
+  if (o && !o->obs) return fail(CA_EINVAL, "cagpu_policy_draw: CaOut given with a NULL obs%s");
+  DrawArgs k;
+  std::memset(&k, 0, sizeof(k));
+  k.flags = s->flags; k.reset_count = s->reset_count; k.obs = o ? o->obs : nullptr; k.mask = env_mask;
+  k.cdf = d->cdf; k.bits = d->policy_bits; k.seed = d->seed;
+  k.env_id_offset = ar->env_id_offset; k.total = static_cast<long>(p->num_envs) * p->num_agents;
+  k.N = p->num_agents; k.W = 6 + 7 * p->max_obs; k.P = d->num_policies; k.ensure = d->ensure; k.ragged = p->ragged;
+  const unsigned grid = static_cast<unsigned>((k.total + 255) / 256);
+  hipLaunchKernelGGL(policy_draw_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), k);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
 }
 
 // The eleven fixed entry points: each is the CaStepEx its arguments spell, plus the record it insists on.

@@ -386,8 +386,29 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
       reset_cnt += 1;
       // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by agent 0's thread
       if (k.map_seed && a == 0) k.env_map[e] = map_draw(k.map_seed, k.env_id_offset + e, reset_cnt, k.num_maps);
+      const long c = (k.env_id_offset + e + static_cast<long>(reset_cnt) * k.case_stride) % k.n_cases;
+      // policy draw (CaPolicyDraw; workgroup-uniform like the branch it sits on): every thread draws its own slot's pool
+      // index once and the env settles the ensure rule through sh_flag (free again: every thread has read the flag words)
+      int drawn = -1;
+      if (k.draw_cdf) {
+        if (active && (!p.ragged || k.table[(c * N + a) * 6 + 5] > 0.0))
+          drawn = draw_index(k.draw_cdf, k.draw_n, draw_uniform(k.draw_seed, k.env_id_offset + e, reset_cnt, static_cast<unsigned>(a)));
+        __syncthreads();
+        sh_flag[a] = static_cast<uint32_t>(drawn);
+        __syncthreads();
+        if (drawn >= 0 && k.draw_ensure >= 0 && drawn != k.draw_ensure) {
+          int n = 0, before = 0;
+          bool any = false;
+          for (int j = 0; j < N; ++j) {
+            const int dj = static_cast<int>(sh_flag[j]);
+            n += static_cast<int>(dj >= 0);
+            before += static_cast<int>(dj >= 0 && j < a);
+            any |= dj == k.draw_ensure;
+          }
+          if (!any && before == draw_ensure_rank(k.draw_seed, k.env_id_offset + e, reset_cnt, n)) drawn = k.draw_ensure;
+        }
+      }
       if (active) {
-        const long c = (k.env_id_offset + e + static_cast<long>(reset_cnt) * k.case_stride) % k.n_cases;
         double h0 = 0.0;
         if (k.heading_seed) {  // test_cases.py:558-559 (training mode): uniform in [-pi, pi)
           const unsigned long long ge = static_cast<unsigned long long>(k.env_id_offset + e);
@@ -405,6 +426,7 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
           eplog_store(k.log_rows, k.log_head, k.log_cap, e, static_cast<int>(c), k.log_case_step, k.n_cases, N, a,
                       reset_cnt - 1, sh_r0[a], sh_r1[a], sh_r2[a], r.flags, ep_step, any_coll, all_goal);
         reset_lane(r, k.table + (c * N + a) * 6, k.heading_seed != 0, h0, p);
+        if (drawn >= 0) r.flags = (r.flags & ~0xFC0u) | (k.draw_bits[drawn] & 0xFC0u);
         statics_dirty = true;
         do_sense = true;
       }

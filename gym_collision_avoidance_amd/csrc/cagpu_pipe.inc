@@ -870,6 +870,15 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
             Lane r;
             r.flags = flags;
             reset_lane(r, k.table + (c * N + a) * 6, false, 0.0, p);
+            // policy draw (CaPolicyDraw; a uniform test inside the FINAL instantiations): the new episode's policy bits of this
+            // slot, every lane recomputing its env's draws; the S-pair's reset copy reads is_learning from sh_flag behind M_CA4
+            if (FINAL && k.draw_cdf) {
+              const double* rad = k.table + c * N * 6 + 5;
+              r.flags = policy_draw_word(k.draw_cdf, k.draw_bits, k.draw_n, k.draw_ensure, k.draw_seed,
+                                         k.env_id_offset + env0 + le, reset_cnt, a, N,
+                                         [&](const int j) { return !ragged || rad[j * 6] > 0.0; }, r.flags);
+              sh_flag[lane] = r.flags;
+            }
             // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by its agent 0 lane
             if (!MULTI && k.map_seed && a == 0) k.env_map[env0 + le] = map_draw(k.map_seed, k.env_id_offset + env0 + le, reset_cnt, k.num_maps);
             px = r.px; py = r.py; vx = r.vx; vy = r.vy; heading = r.heading;

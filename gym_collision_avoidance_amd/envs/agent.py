@@ -72,6 +72,19 @@ class Agent(object):
         i = self._init
         return [i["px"], i["py"], i["gx"], i["gy"], i["pref_speed"], i["radius"]], i["heading"]
 
+    # the policy object: the agent's own -- or, for the view of a batch slot whose policies are drawn on the device at every
+    # auto-reset (set_fixture_suite(policy_distr=...)), the pool's object the slot's flag word names right now
+    @property
+    def policy(self):
+        env = self._env
+        if env is not None and env._policy_pool is not None:
+            return env._drawn_policy(self._e, self._a, self._policy)
+        return self._policy
+
+    @policy.setter
+    def policy(self, value):
+        self._policy = value
+
     def _bind(self, env, e, a):
         self._env, self._e, self._a = env, e, a
         self._history = []

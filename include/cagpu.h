@@ -645,6 +645,53 @@ int cagpu_rollout_log(const CaParams *p, const CaState *s, const CaOut *o, const
                       int32_t n_steps, int32_t ring, int64_t snapshot_delta, const CaTraj *traj, const CaFinal *fin,
                       const CaEpLog *log, void *stream);
 
+/* POLICY DRAW (additive to v12; cagpu_step_draw / cagpu_policy_draw): which policy every agent of a NEW episode runs, drawn
+ * at the auto-reset itself -- the batched form of test_cases.py cadrl_test_case_to_agents,
+ *     names = np.random.choice(policies, num_agents, p=policy_distr)
+ *     if policy_to_ensure not in names: names[np.random.randint(len(names))] = policy_to_ensure
+ * THE RULE, stated once.  For env e: g = CaAutoReset.env_id_offset + e (the global env id), k = CaState.reset_count[e] of
+ * the new episode (AFTER the auto-reset's increment), u(c) = the Philox4x32-10 uniform of key `seed` and counter
+ * (g lo, g hi, k, c) -- the construction of CaAutoReset.heading_seed's draws.  The PRESENT slots are those whose new case
+ * row has radius > 0 (every slot unless CaParams.ragged).
+ *   1. present slot a draws pool index j_a = #{j : cdf[j] <= u(a)}, clamped to P - 1 (np.searchsorted(cdf, u, 'right'):
+ *      what np.random.choice does);
+ *   2. if ensure >= 0 and no present slot drew `ensure`: r = min(floor(n u(0xFFFFFFFE)), n - 1), n the number of present
+ *      slots, and the r-th present slot in slot order takes `ensure`;
+ *   3. a present slot's flag word becomes (flags & ~0xFC0) | policy_bits[j]; absent slots keep theirs.
+ * A pure function of (seed, g, k): single launches, cagpu_rollout, a ring, a rewind's replay and every shard layout draw
+ * the same bits, and no lane needs another lane's result (each recomputes its env's draws; the large-env kernel shares them
+ * through LDS).  Bits 12 and up (dynamics, CA_ABSENT, CA_PLAN_VALID) and bits 0 - 5 are never touched by the draw. */
+typedef struct CaPolicyDraw {
+  const double   *cdf;          /* device [P]: cumsum(policy_distr) / its last element, as np.random.choice computes it */
+  const uint32_t *policy_bits;  /* device [P]: bits 6..11 of the flag word of pool entry j (CA_IS_LEARNING,
+                                   CA_STILL_LEARNING, the policy id); other bits are ignored */
+  int32_t         num_policies; /* P in 1..8 */
+  int32_t         ensure;       /* -1, or the pool index every episode must hold */
+  uint64_t        seed;         /* != 0, and != CaAutoReset.heading_seed (equal keys would make the heading and the policy
+                                   of an agent the same uniform) */
+} CaPolicyDraw;                 /* 32 bytes */
+
+/* cagpu_step_ex + the draw at every auto-reset of the call.  d == NULL: exactly cagpu_step_ex.  Otherwise CA_EINVAL, nothing
+ * launched (reported behind "snapshot_delta without ring" and ahead of the records): d->cdf or d->policy_bits NULL,
+ * num_policies outside 1..8, ensure outside -1 .. P - 1, seed == 0, ar == NULL (no table, no auto-reset, nothing is ever
+ * drawn), seed == ar->heading_seed.  Everything of `x` holds as in cagpu_step_ex (a map or a map set: single steps only).
+ * With the draw on, CaAutoReset.reset_plan is not used (a plan belongs to the policy it was made for): an env that reset
+ * starts its episode without a valid plan and is queried on the pre-move state; column 0 (is_learning) of a row copied from
+ * CaAutoReset.reset_obs is written from the drawn bits.  The pipelined kernels draw in their " final" instantiations
+ * (cagpu_last_kernel() shows " draw"); without a draw no kernel selection and no kernel code changes. */
+int cagpu_step_draw(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
+                    const CaStepEx *x, const CaPolicyDraw *d, void *stream);
+
+/* The same rule applied to the CURRENT state, for the episode k = reset_count[e] each env is in (after cagpu_reset: k = 0,
+ * which also needs its lottery) -- a small kernel of its own, envs with env_mask[e] == 0 untouched (NULL: all).  Present
+ * slots are those without CA_ABSENT (every slot unless CaParams.ragged); their flag words are rewritten by step 3 and lose
+ * CA_PLAN_VALID (a plan belongs to the policy it was made for).  o != NULL: column 0 of the present slots' rows of o->obs
+ * is rewritten from the drawn bits as well (o->obs only; the other members are not read).  Of `ar` only env_id_offset and
+ * heading_seed are read.  CA_EINVAL, nothing launched: what cagpu_step_draw rejects of d and ar, NULL p / s / d, bad sizes,
+ * NULL s->flags / s->reset_count, o given with o->obs NULL. */
+int cagpu_policy_draw(const CaParams *p, const CaState *s, const CaOut *o, const CaAutoReset *ar, const CaPolicyDraw *d,
+                      const uint8_t *env_mask, void *stream);
+
 /* The policy query of the NEXT step ahead of time (collision_avoidance_env.py:305-323 for the built-in RVO policy):
  * fills s->next_action from the CURRENT state and sets CA_PLAN_VALID, without stepping.  cagpu_step / cagpu_rollout keep
  * the plan up to date by themselves; this entry point exists for states that did not come out of a step (the reset state
