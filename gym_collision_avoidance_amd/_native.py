@@ -97,6 +97,17 @@ class CaPolicyDraw(C.Structure):
     _fields_ = [("cdf", _P), ("policy_bits", _P), ("num_policies", C.c_int32), ("ensure", C.c_int32), ("seed", C.c_uint64)]
 
 
+class CaCaseStream(C.Structure):
+    """a case stream (cagpu_stream_refill): the window table of a CaAutoReset and what keeps it ahead of the envs;
+    include/cagpu.h states the rule.  side_ranges is a HOST pointer: whoever stores it keeps that array alive"""
+    _fields_ = [("table", _P), ("held", _P), ("seen", _P), ("work_index", _P), ("work_row", _P), ("work_count", _P),
+                ("counts", _P), ("status", _P), ("window", C.c_int32), ("n_min", C.c_int32), ("n_max", C.c_int32),
+                ("n_ranges", C.c_int32), ("side_ranges", _P), ("speed_lo", C.c_double), ("speed_hi", C.c_double),
+                ("radius_lo", C.c_double), ("radius_hi", C.c_double), ("seed", C.c_uint64)]
+
+
+FAULT_STREAM_OVERRUN = 8   # bit 3 of the fault word: an env of a case stream ran past its window between two refills
+
 POLICY_DRAW_BITS = 0xFC0   # the bits of a flag word a draw rewrites: IS_LEARNING, STILL_LEARNING, the policy id
 
 
@@ -133,7 +144,8 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_step_maps", "cagpu_laserscan_maps", "cagpu_occupancy_grid", "cagpu_occupancy_grid_maps",
            "cagpu_step_traj", "cagpu_rollout_traj", "cagpu_step_final", "cagpu_rollout_final",
            "cagpu_step_log", "cagpu_rollout_log", "cagpu_step_ex", "cagpu_step_draw", "cagpu_policy_draw",
-           "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes", "cagpu_ga3c_query", "cagpu_ga3c_value")
+           "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes", "cagpu_ga3c_query", "cagpu_ga3c_value",
+           "cagpu_generate_cases_at", "cagpu_stream_refill")
 
 _lib = None
 
@@ -197,6 +209,9 @@ def lib():
     L.cagpu_generate_cases.argtypes = [C.c_int64, C.c_int32] + [C.c_double] * 6 + [C.c_uint64, _P, _P, _P]
     L.cagpu_generate_cases_ragged.argtypes = ([C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32] + [C.c_double] * 4 +
                                               [C.c_uint64, _P, _P, _P, _P])
+    L.cagpu_generate_cases_at.argtypes = ([_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32] +
+                                          [C.c_double] * 4 + [C.c_uint64, _P, _P, _P, _P])
+    L.cagpu_stream_refill.argtypes = [PP, PS, PA, C.POINTER(CaCaseStream), _P]
     L.cagpu_device_faults.argtypes = [_P, C.c_int32]
     L.cagpu_device_faults_async.argtypes = [_P, _P]
     L.cagpu_workspace_bytes.argtypes = [PP]

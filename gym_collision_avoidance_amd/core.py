@@ -179,6 +179,8 @@ class BatchedSim(object):
         # the episode log (log_episodes): None = off; dict(rows [E, C, N, 4] f64, head [E, C, 4] i32, cursor [E] i64, cap)
         self._log = None
         self._cl = nat.CaEpLog()
+        # the case stream (set_case_stream): None = off; dict(c=CaCaseStream, ref, its tensors, every, since, dist)
+        self._cstream = None
 
     # ---------------------------------------------------------------- what the outside reads
     # `state` and the four outputs are those of the step last handed out: reading them goes through sync(), which rewinds a
@@ -476,6 +478,144 @@ class BatchedSim(object):
         res = (out,) + ((status,) if return_status else ()) + ((counts,) if return_counts else ())
         return res if len(res) > 1 else out
 
+    @staticmethod
+    def _case_dist(N, side_length, num_agents):
+        """the generator's distribution arguments in the form cagpu_generate_cases_at takes them -> (n_min, n_max,
+        host float64 array, n_ranges); the same mapping generate_cases() applies to its two entry points"""
+        if num_agents is None and not isinstance(side_length, list):
+            lo, hi = (side_length, side_length) if np.isscalar(side_length) else side_length
+            return 0, 0, np.ascontiguousarray([lo, hi], dtype=np.float64), 0
+        n_lo, n_hi = (N, N) if num_agents is None else (int(num_agents[0]), int(num_agents[1]))
+        if isinstance(side_length, list):
+            rg = [[c["num_agents"][0], c["num_agents"][1], c["side_length"][0], c["side_length"][1]] for c in side_length]
+        else:
+            lo, hi = (side_length, side_length) if np.isscalar(side_length) else side_length
+            rg = [[0, 1 << 30, lo, hi]]
+        rg = np.ascontiguousarray(rg, dtype=np.float64)
+        return n_lo, n_hi, rg, len(rg)
+
+    def generate_cases_at(self, case_index, seed, side_length=4.0, speed_bnds=(0.5, 2.0), radius_bnds=(0.2, 0.8),
+                          num_agents=None, out=None, out_row=None, count=None, counts=None, status=None,
+                          return_status=False, return_counts=False):
+        """The scenarios of the given 64-bit case indices (cagpu_generate_cases_at: one wave per case, bit for bit what
+        generate_cases() gives the same (seed, index)): `case_index` int64 [M] (device tensor or array-like); the
+        distribution arguments are those of generate_cases().  Entry m lands in row out_row[m] of `out` (default: a new
+        [M, N, 6] table, row m); `count`: a device int32 [1] tensor -- only the first min(count, M) entries are
+        generated, read on the device.  `counts` / `status`: int32 tensors of out's rows to write into (default: new)."""
+        ci = self._dev(case_index, torch.int64).reshape(-1)
+        M = int(ci.shape[0])
+        if out is None:
+            if out_row is not None:
+                raise ValueError("generate_cases_at: out_row needs the table `out` its rows index")
+            out = torch.zeros((M, self.N, 6), dtype=torch.float64, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape[1:]) == (self.N, 6), out.shape
+        R = int(out.shape[0])
+        rows = self._dev(out_row, torch.int64)
+        if rows is not None:
+            rows = rows.reshape(-1)
+            # (a convenience call, not the product path: the rows are checked here, the kernel trusts them)
+            if int(rows.shape[0]) != M or (M and (int(rows.min()) < 0 or int(rows.max()) >= R)):
+                raise ValueError("generate_cases_at: out_row must hold %d rows inside [0, %d)" % (M, R))
+        elif M > R:
+            raise ValueError("generate_cases_at: %d cases do not fit a table of %d rows" % (M, R))
+        counts = torch.zeros((R,), dtype=torch.int32, device=self.device) if counts is None else counts
+        status = torch.zeros((R,), dtype=torch.int32, device=self.device) if status is None else status
+        assert counts.shape[0] == R and status.shape[0] == R and counts.dtype == status.dtype == torch.int32
+        n_lo, n_hi, rg, n_rg = self._case_dist(self.N, side_length, num_agents)
+        sp = (float(speed_bnds[0]), float(speed_bnds[1]), float(radius_bnds[0]), float(radius_bnds[1]))
+        nat.check(self.lib.cagpu_generate_cases_at(ci.data_ptr() if M else None, None if rows is None else rows.data_ptr(),
+                                                   None if count is None else count.data_ptr(), M, self.N, n_lo, n_hi,
+                                                   rg.ctypes.data, n_rg, *sp, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                   out.data_ptr(), counts.data_ptr(), status.data_ptr(), self._stream()))
+        self._keep = [ci, rows, count]   # keep alive until the stream has consumed them
+        res = (out,) + ((status,) if return_status else ()) + ((counts,) if return_counts else ())
+        return res if len(res) > 1 else out
+
+    def set_case_stream(self, window=8, seed=0, side_length=4.0, speed_bnds=(0.5, 2.0), radius_bnds=(0.2, 0.8),
+                        num_agents=None, heading_seed=0, env_id_offset=0):
+        """A FRESH random scenario at every on-device auto-reset (include/cagpu.h CaCaseStream) -- the reference's default
+        training configuration, Config.TEST_CASE_FN = "get_testcase_random", which builds a new scenario at every reset():
+        episode k of the env with global id g = env_id_offset + e runs scenario(seed, case index (g << 32) | k) of the
+        device generator (the distribution arguments are those of generate_cases(); `num_agents=(lo, hi)` needs a sim
+        built with ragged=1), whatever the batch size, the sharding, the window or the launch pattern.  The auto-reset
+        table becomes a window of `window` upcoming episodes per env ([E * window, N, 6], case_stride = E), and a refill
+        (cagpu_stream_refill, no host synchronisation) regenerates the used-up rows ahead of every rollout() and ring
+        launch, every max(1, window - 1) single steps and after a host reset().  An env that auto-resets more than
+        `window` times between two refills repeats a scenario and raises bit 3 of the fault word (check_faults()).
+        Policy draw, final record, episode log, trajectory tape and map set attach to it as to a fixture table (the
+        episode log's `case` is the window row; stream_case_index() names the scenario).  window=None: detach, like
+        set_fixture_table(None).  A host reset restarts the envs it touches at episode 0: they REPLAY their sequence
+        unless `seed` is changed, like cases, headings and policies today."""
+        self.sync()
+        if self._la is not None:
+            self._la["in_kernel"].clear()
+            self._la["prep"] = None
+        if window is None:
+            self._cstream = None
+            self.set_fixture_table(None)
+            return
+        E, N, W, dev = self.E, self.N, int(window), self.device
+        if W < 1 or E * W > 0x7FFFFFFF:
+            raise ValueError("set_case_stream: window must be >= 1 and num_envs * window < 2^31")
+        off = int(env_id_offset)
+        if off < 0 or off + E > 1 << 32:
+            raise ValueError("set_case_stream: global env ids (env_id_offset + e) must be < 2^32")
+        if num_agents is not None and not self.p.ragged:
+            raise ValueError("set_case_stream: num_agents=(lo, hi) draws an agent count per episode -- build the sim with ragged=1")
+        hs = int(heading_seed) & 0xFFFFFFFFFFFFFFFF
+        if self._draw is not None and self._draw["c"].seed == hs:
+            raise ValueError("heading_seed equals the policy draw's seed: an agent's heading and policy would be the same uniform")
+        n_lo, n_hi, rg, n_rg = self._case_dist(N, side_length, num_agents)
+        t = dict(table=torch.zeros((E * W, N, 6), dtype=torch.float64, device=dev),
+                 held=torch.full((E, W), -1, dtype=torch.int32, device=dev),
+                 seen=torch.zeros((E,), dtype=torch.int32, device=dev),
+                 work_index=torch.zeros((E * W,), dtype=torch.int64, device=dev),
+                 work_row=torch.zeros((E * W,), dtype=torch.int64, device=dev),
+                 work_count=torch.zeros((1,), dtype=torch.int32, device=dev),
+                 counts=torch.zeros((E * W,), dtype=torch.int32, device=dev),
+                 status=torch.zeros((E * W,), dtype=torch.int32, device=dev))
+        c = nat.CaCaseStream(window=W, n_min=n_lo, n_max=n_hi, n_ranges=n_rg, side_ranges=rg.ctypes.data,
+                             speed_lo=float(speed_bnds[0]), speed_hi=float(speed_bnds[1]), radius_lo=float(radius_bnds[0]),
+                             radius_hi=float(radius_bnds[1]), seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                             **{k_: v.data_ptr() for k_, v in t.items()})
+        self._table, self._reset_obs, self._reset_plan = None, None, None
+        self._ar = nat.CaAutoReset(table=t["table"].data_ptr(), n_cases=E * W, env_id_offset=off, case_stride=E,
+                                   reset_obs=None, reset_plan=None, heading_seed=hs)
+        self._ar_ref = C.byref(self._ar)
+        self._cstream = dict(c=c, ref=C.byref(c), t=t, rg=rg, W=W, every=max(1, W - 1), since=0, refills=0,
+                             refill=self.lib.cagpu_stream_refill,
+                             dist=dict(side_length=side_length, speed_bnds=tuple(speed_bnds), radius_bnds=tuple(radius_bnds),
+                                       num_agents=num_agents), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, off=off)
+        self._stream_refill()   # the window holds the episodes behind the one every env is in from here on
+
+    def _stream_refill(self):
+        """cagpu_stream_refill on the current stream.  Called only where the device state is the state LAST HANDED OUT
+        (after sync(): ahead of a rollout / ring launch, between single steps, after a host reset).  INVARIANT: a refill
+        replaces only rows of episodes <= the handed-out reset_count -- episodes that were loaded already -- and a rewind
+        goes back to a snapshot taken BEHIND a refill, so the replay of a rewind never needs a replaced row."""
+        st = self._cstream
+        rc = st["refill"](self._p_ref, self._cs_ref, self._ar_ref, st["ref"], self._stream_handle())
+        if rc != 0:
+            nat.check(rc)
+        st["since"] = 0
+        st["refills"] += 1
+
+    def stream_case_index(self, env, episode):
+        """the 64-bit case index of episode `episode` of this shard's env `env` under the attached stream (ints or
+        integer arrays, broadcast): (global env id << 32) | episode -- what generate_cases_at() takes"""
+        assert self._cstream is not None, "set_case_stream() first"
+        g = np.asarray(env, np.int64) + self._cstream["off"]
+        out = (g << 32) | np.asarray(episode, np.int64)
+        return int(out) if out.ndim == 0 else out
+
+    def reset_from_stream(self):
+        """Initial load under a case stream: every env <- episode 0 of its own sequence (cagpu_generate_cases_at + cagpu_reset),
+        and the window filled with the episodes behind it."""
+        st = self._cstream
+        assert st is not None, "set_case_stream() first"
+        idx = (torch.arange(self.E, device=self.device, dtype=torch.int64) + st["off"]) << 32
+        return self.reset(self.generate_cases_at(idx, st["seed"], **st["dist"]))
+
     def set_fixture_table(self, table, env_id_offset=0, case_stride=None, heading_seed=0):
         """Enable DummyVecEnv-style auto-reset from a fixture table [C,N,6] (vec_env.py:120-128,
         test_cases.py:593-624): env e's k-th reset loads case (env_id_offset + e + k*case_stride) % C.
@@ -485,6 +625,7 @@ class BatchedSim(object):
         if self._la is not None:
             self._la["in_kernel"].clear()
             self._la["prep"] = None
+        self._cstream = None    # (a table, or none, replaces a case stream)
         if table is None:
             self._ar, self._ar_ref, self._table = None, None, None
             if self._draw is not None:  # (no auto-reset, nothing is ever drawn: the policy draw goes with the table)
@@ -600,6 +741,8 @@ class BatchedSim(object):
         if self._draw is not None:   # episode 0 of the envs this reset touches needs its lottery too
             self._policy_draw_now(m)
         self._keep = [c, h, m]  # keep alive until the stream has consumed them
+        if self._cstream is not None:   # the reset envs restart at episode 0: their window holds episodes 1 .. W again
+            self._stream_refill()
         if self._log is not None:   # the reset envs count their episodes from 0 again: undrained records of theirs are discarded
             episodes.clear(self._log["head"], self._log["cursor"], m)
         if self._traj is not None:   # a host-side reset logs no row but ends the episode of the envs it touches (tape "epoch")
@@ -792,6 +935,10 @@ class BatchedSim(object):
             ext = None if e is None else e.data_ptr()
         if self.fresh_outputs:
             self._new_outputs()
+        if self._cstream is not None:   # a case stream: an env ends at most one episode per step
+            if self._cstream["since"] >= self._cstream["every"]:
+                self._stream_refill()
+            self._cstream["since"] += 1
         rc = self._launch(self._p_ref, self._cs_ref, self._co_ref, ext, self._ar_ref, self._sx_ref, self._stream_handle())
         if rc != 0:
             nat.check(rc)
@@ -817,6 +964,8 @@ class BatchedSim(object):
         e = self._dev(ext_actions, torch.float64)
         if self.fresh_outputs:
             self._new_outputs()
+        if self._cstream is not None:
+            self._stream_refill()
         # the n steps' CaStepEx: no map (as ever), the tape's own chunk, the single-step final block -- it ends up holding every
         # env's most recent terminal record of the launch -- and the log, every ending in its own slot
         chunk, ct = self._traj_chunk(int(n_steps)) if self._traj_on else (None, None)
@@ -891,6 +1040,8 @@ class BatchedSim(object):
                                  "draws, sensor variants or a static map) -- use step()")
         if self._cs.ext_state:   # (CaState.ext_state belongs to the ONE step() call that was given it: see rollout())
             self._cs.ext_state, self._ext_state = None, None
+        if self._cstream is not None:   # (a ring is launched only when the previous one is used up or sync() has rewound)
+            self._stream_refill()
         rec = self._traj_on      # (one look per fill: with recording off a fill does what it did before the tape existed)
         if rec:
             fit = self._traj_fit()   # (a full tape raises here, before anything changes)
@@ -1006,6 +1157,8 @@ class BatchedSim(object):
         t, k = la["t"], la["len"]
         obs, rew, done, over = la["ring"]
         la["slots"] = None
+        if self._cstream is not None:   # up to k steps since the ring's refill: the next single step refills first
+            self._cstream["since"] = self._cstream["every"]
         if t < k:
             la["rewinds"] += 1
             if la["adaptive"]:     # the caller came back after t steps: that is how far the next ring looks ahead
@@ -1413,10 +1566,12 @@ class BatchedSim(object):
         with torch.cuda.device(self.device):
             f = nat.device_faults(clear=True)
         if f:
-            raise nat.CagpuError("device fault word 0x%x:%s%s%s the simulator state is not to be trusted" % (
+            raise nat.CagpuError("device fault word 0x%x:%s%s%s%s the simulator state is not to be trusted" % (
                 f, " a hand-over inside the pipelined step kernel timed out;" if f & 1 else "",
                 " a GA3C-CADRL operand left the fp16 range of the network kernel's two-plane split (|x| >= 65504);" if f & 2 else "",
-                " bit 2: a map-set env's map index (env_map) lay outside [0, num_maps), that env saw an empty map;" if f & 4 else ""))
+                " bit 2: a map-set env's map index (env_map) lay outside [0, num_maps), that env saw an empty map;" if f & 4 else "",
+                " bit 3: an env of a case stream auto-reset more than `window` times between two refills and repeated a "
+                "scenario (set_case_stream: a larger window, or shorter launches);" if f & 8 else ""))
 
     def episode_stats(self, check=True):
         """Per-shard episode counters: float64 [8] (see STAT_NAMES), reduced on the device.  A reporting point: the

@@ -554,7 +554,8 @@ __device__ double time_to_impact(double hx, double hy, double ox, double oy, dou
 
 // The device's fault word (cagpu_device_faults; defined above KArgs' set_grid): bit 0 = a bounded hand-over poll of the
 // pipelined step kernel ran out (cagpu_pipe.inc), bit 1 = a GA3C-CADRL operand left the fp16 range of the network kernel's
-// two-plane split (cagpu_ga3c.inc), bit 2 = a map-set env's map index lay outside [0, num_maps) (set_grid).
+// two-plane split (cagpu_ga3c.inc), bit 2 = a map-set env's map index lay outside [0, num_maps) (set_grid), bit 3 = an env of
+// a case stream ran past its window between two refills (cagpu_gen.inc stream_refill_kernel).
 
 #include "cagpu_grouplp.inc"
 
@@ -2882,46 +2883,141 @@ int ga3c_impl(const CaParams* p, const CaState* s, const float* obs, const CaNet
 }
 }  // namespace
 
-static int generate_impl(int64_t num_cases, int32_t num_agents, int32_t n_min, int32_t n_max, const double* side_ranges,
-                         int32_t n_ranges, double side_lo, double side_hi, double speed_lo, double speed_hi, double radius_lo,
-                         double radius_hi, uint64_t seed, double* cases, int32_t* counts, int32_t* status, void* stream) {
-  if (num_cases < 1 || num_agents < 1 || num_agents > 4096) return fail(CA_EINVAL, "cagpu_generate_cases: bad sizes%s");
-  if (!cases) return fail(CA_EINVAL, "cagpu_generate_cases: NULL cases%s");
+// the generator's argument block from the entry points' arguments; `plain` / `ragged` name the caller in the messages
+static int gen_fail(const char* who, const char* text) {
+  std::snprintf(g_err, sizeof(g_err), "%s: %s", who, text);
+  return CA_EINVAL;
+}
+
+static int generate_args(gen::Args& a, const char* plain, const char* ragged, int32_t num_agents, int32_t n_min, int32_t n_max,
+                         const double* side_ranges, int32_t n_ranges, double side_lo, double side_hi, double speed_lo,
+                         double speed_hi, double radius_lo, double radius_hi, uint64_t seed, double* cases, int32_t* counts,
+                         int32_t* status) {
+  if (!cases) return gen_fail(plain, "NULL cases");
   if (!(side_lo > 0.0) || !(side_hi >= side_lo) || !(speed_lo > 0.0) || !(speed_hi >= speed_lo) || !(radius_lo > 0.0) ||
       !(radius_hi >= radius_lo))
-    return fail(CA_EINVAL, "cagpu_generate_cases: bounds must be positive and ordered%s");
-  gen::Args a;
+    return gen_fail(plain, "bounds must be positive and ordered");
   std::memset(&a, 0, sizeof(a));
-  a.cases = cases; a.status = status; a.C = num_cases; a.N = num_agents;
+  a.cases = cases; a.status = status; a.N = num_agents;
   a.side_lo = side_lo; a.side_hi = side_hi; a.speed_lo = speed_lo; a.speed_hi = speed_hi;
   a.radius_lo = radius_lo; a.radius_hi = radius_hi; a.seed = seed;
   a.max_attempts = 20000;  // the reference loops until a sample is accepted (its square / circle grows 1 % per retry)
   a.counts = counts;
   if (n_max > 0) {
-    if (n_min < 1 || n_min > n_max || n_max > num_agents)
-      return fail(CA_EINVAL, "cagpu_generate_cases_ragged: need 1 <= n_min <= n_max <= max_agents%s");
+    if (n_min < 1 || n_min > n_max || n_max > num_agents) return gen_fail(ragged, "need 1 <= n_min <= n_max <= max_agents");
     a.n_min = n_min; a.n_max = n_max;
   }
   if (n_ranges > 0) {
-    if (n_ranges > 8 || !side_ranges) return fail(CA_EINVAL, "cagpu_generate_cases_ragged: at most 8 side ranges%s");
+    if (n_ranges > 8 || !side_ranges) return gen_fail(ragged, "at most 8 side ranges");
     for (int r = 0; r < n_ranges; ++r) {
       for (int k = 0; k < 4; ++k) a.ranges[r][k] = side_ranges[r * 4 + k];
       if (!(a.ranges[r][2] > 0.0) || !(a.ranges[r][3] >= a.ranges[r][2]))
-        return fail(CA_EINVAL, "cagpu_generate_cases_ragged: side ranges must be positive and ordered%s");
+        return gen_fail(ragged, "side ranges must be positive and ordered");
     }
     a.n_ranges = n_ranges;
     // the reference asserts that some entry holds the drawn count (test_cases.py:241)
     for (int n = (n_max > 0 ? n_min : num_agents); n <= (n_max > 0 ? n_max : num_agents); ++n) {
       bool held = false;
       for (int r = 0; r < n_ranges; ++r) held = held || (a.ranges[r][0] <= n && n < a.ranges[r][1]);
-      if (!held) return fail(CA_EINVAL, "cagpu_generate_cases_ragged: an agent count in [n_min, n_max] has no side range%s");
+      if (!held) return gen_fail(ragged, "an agent count in [n_min, n_max] has no side range");
     }
   }
+  return CA_OK;
+}
+
+static int generate_impl(int64_t num_cases, int32_t num_agents, int32_t n_min, int32_t n_max, const double* side_ranges,
+                         int32_t n_ranges, double side_lo, double side_hi, double speed_lo, double speed_hi, double radius_lo,
+                         double radius_hi, uint64_t seed, double* cases, int32_t* counts, int32_t* status, void* stream) {
+  if (num_cases < 1 || num_agents < 1 || num_agents > 4096) return fail(CA_EINVAL, "cagpu_generate_cases: bad sizes%s");
+  gen::Args a;
+  const int rc = generate_args(a, "cagpu_generate_cases", "cagpu_generate_cases_ragged", num_agents, n_min, n_max, side_ranges,
+                               n_ranges, side_lo, side_hi, speed_lo, speed_hi, radius_lo, radius_hi, seed, cases, counts, status);
+  if (rc != CA_OK) return rc;
+  a.C = num_cases;
   hipLaunchKernelGGL(gen::generate_kernel, dim3(static_cast<unsigned>((num_cases + 63) / 64)), dim3(64), 0,
                      static_cast<hipStream_t>(stream), a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
   return CA_OK;
+}
+
+// the wave-per-case launch over a list (cagpu_generate_cases_at, cagpu_stream_refill): grid and block depend on M only
+static int launch_generate_at(const gen::Args& a, const int64_t* case_index, const int64_t* out_row, const int32_t* count,
+                              int64_t M, void* stream) {
+  gen::AtArgs q;
+  q.a = a;
+  q.case_index = reinterpret_cast<const long long*>(case_index);
+  q.out_row = reinterpret_cast<const long long*>(out_row);
+  q.count = count; q.M = static_cast<long>(M);
+  const int64_t cap = 16L * device_cus();
+  const unsigned grid = static_cast<unsigned>(M < cap ? M : cap);
+  const size_t lds = static_cast<size_t>(a.N) * 6 * sizeof(double);
+  hipLaunchKernelGGL(gen::generate_at_kernel, dim3(grid), dim3(64), lds, static_cast<hipStream_t>(stream), q);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
+}
+
+// side_ranges of the _at / stream form: n_ranges == 0 means HOST [2] = side lo, hi (the plain form of cagpu_generate_cases)
+static int generate_at_args(gen::Args& a, const char* who, int32_t max_agents, int32_t n_min, int32_t n_max,
+                            const double* side_ranges, int32_t n_ranges, double speed_lo, double speed_hi, double radius_lo,
+                            double radius_hi, uint64_t seed, double* cases, int32_t* counts, int32_t* status) {
+  if (max_agents < 1 || max_agents > 1024) return gen_fail(who, "max_agents must be in 1..1024");
+  if (n_ranges < 0 || !side_ranges) return gen_fail(who, "side_ranges is NULL or n_ranges < 0");
+  if (n_max < 0) return gen_fail(who, "need 1 <= n_min <= n_max <= max_agents");
+  const bool plain = n_ranges == 0;
+  return generate_args(a, who, who, max_agents, n_min, n_max, plain ? nullptr : side_ranges, n_ranges,
+                       plain ? side_ranges[0] : 1.0, plain ? side_ranges[1] : 1.0, speed_lo, speed_hi, radius_lo, radius_hi, seed,
+                       cases, counts, status);
+}
+
+int cagpu_generate_cases_at(const int64_t* case_index, const int64_t* out_row, const int32_t* count, int64_t M,
+                            int32_t max_agents, int32_t n_min, int32_t n_max, const double* side_ranges, int32_t n_ranges,
+                            double speed_lo, double speed_hi, double radius_lo, double radius_hi, uint64_t seed, double* cases,
+                            int32_t* counts, int32_t* status, void* stream) {
+  const char* who = "cagpu_generate_cases_at";
+  if (M < 1 || M > 0x7FFFFFFFL) return gen_fail(who, "the list needs 1 .. 2^31 - 1 entries");
+  if (!case_index) return gen_fail(who, "NULL case_index");
+  gen::Args a;
+  const int rc = generate_at_args(a, who, max_agents, n_min, n_max, side_ranges, n_ranges, speed_lo, speed_hi, radius_lo,
+                                  radius_hi, seed, cases, counts, status);
+  if (rc != CA_OK) return rc;
+  return launch_generate_at(a, case_index, out_row, count, M, stream);
+}
+
+int cagpu_stream_refill(const CaParams* p, const CaState* s, const CaAutoReset* ar, const CaCaseStream* cs, void* stream) {
+  const char* who = "cagpu_stream_refill";
+  if (!p || !s || !ar || !cs) return gen_fail(who, "NULL argument");
+  if (p->num_envs < 1 || p->num_agents < 1) return gen_fail(who, "bad sizes");
+  if (!s->reset_count) return gen_fail(who, "NULL state pointer (reset_count)");
+  if (cs->window < 1) return gen_fail(who, "window must be >= 1");
+  const int64_t rows = static_cast<int64_t>(p->num_envs) * cs->window;
+  if (rows > 0x7FFFFFFFL) return gen_fail(who, "num_envs * window does not fit CaAutoReset.n_cases");
+  if (!cs->table || !cs->held || !cs->seen || !cs->work_index || !cs->work_row || !cs->work_count)
+    return gen_fail(who, "NULL pointer in CaCaseStream (table, held, seen, work_index, work_row, work_count)");
+  if (ar->table != cs->table || ar->n_cases != rows || ar->case_stride != p->num_envs)
+    return gen_fail(who, "the CaAutoReset must name the window: table = CaCaseStream.table, n_cases = num_envs * window, "
+                         "case_stride = num_envs");
+  if (ar->reset_obs || ar->reset_plan)
+    return gen_fail(who, "reset_obs / reset_plan of a stream's CaAutoReset must be NULL (the rows change under them)");
+  if (ar->env_id_offset < 0 || ar->env_id_offset + p->num_envs > (1LL << 32))
+    return gen_fail(who, "global env ids (env_id_offset + e) must be < 2^32");
+  gen::Args a;
+  const int rc = generate_at_args(a, who, p->num_agents, cs->n_min, cs->n_max, cs->side_ranges, cs->n_ranges, cs->speed_lo,
+                                  cs->speed_hi, cs->radius_lo, cs->radius_hi, cs->seed, cs->table, cs->counts, cs->status);
+  if (rc != CA_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipError_t e = hipMemsetAsync(cs->work_count, 0, sizeof(int32_t), st);
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu_stream_refill: %s", hipGetErrorString(e));
+  gen::RefillArgs r;
+  r.E = p->num_envs; r.W = cs->window; r.env_id_offset = ar->env_id_offset;
+  r.reset_count = s->reset_count; r.held = cs->held; r.seen = cs->seen;
+  r.work_index = reinterpret_cast<long long*>(cs->work_index); r.work_row = reinterpret_cast<long long*>(cs->work_row);
+  r.work_count = cs->work_count;
+  hipLaunchKernelGGL(gen::stream_refill_kernel, dim3(static_cast<unsigned>((rows + 255) / 256)), dim3(256), 0, st, r);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return launch_generate_at(a, cs->work_index, cs->work_row, cs->work_count, rows, stream);
 }
 
 int cagpu_generate_cases(int64_t num_cases, int32_t num_agents, double side_lo, double side_hi, double speed_lo,

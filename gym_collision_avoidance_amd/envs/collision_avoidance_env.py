@@ -167,6 +167,11 @@ class CollisionAvoidanceEnv(Env):
         the host.  With `num_agents=(lo, hi)` in the dict every case also draws its own agent count (the reference's
         num_agents=None; `side_length` may then be the reference's list of {"num_agents", "side_length"} range dicts):
         a ragged table whose short cases leave their last slots empty.
+        With `stream=True` in the dict (and `window=8` instead of num_cases) there is no finite table at all: every
+        on-device auto-reset loads a FRESH scenario of the same generator (core.BatchedSim.set_case_stream) -- episode k of
+        the env with global id env_id_offset + e is scenario (seed, (id << 32) | k) -- which together with
+        `random_headings` and `policy_distr` is the reference's default TEST_CASE_ARGS on the device.  Needs auto_reset;
+        `case_stride` is not used (a stream's stride is the batch size).
         `random_headings` (default: `not Config.EVALUATE_MODE`, the reference's rule, test_cases.py:553-559): initial
         headings -- at reset() and at every on-device auto-reset -- are uniform in [-pi, pi) instead of pointing at the
         goal; drawn on the device from `heading_seed`.
@@ -202,7 +207,12 @@ class CollisionAvoidanceEnv(Env):
                         seed=policy_seed)
         elif policy_to_ensure is not None:
             raise ValueError("policy_to_ensure without policy_distr")
-        if generate is not None:
+        if generate is not None and generate.get("stream"):
+            if table is not None or "seed" not in generate or not auto_reset:
+                raise ValueError("generate=dict(stream=True, ...) needs a seed and auto_reset, and takes no table")
+            if "num_cases" in generate or int(generate.get("window", 8)) < 1:
+                raise ValueError("generate=dict(stream=True, ...) takes window >= 1, not num_cases: a stream has no finite table")
+        elif generate is not None:
             assert table is None and int(generate["num_cases"]) >= 1 and "seed" in generate
             table = None
         elif table is None:
@@ -348,9 +358,14 @@ class CollisionAvoidanceEnv(Env):
                 from gym_collision_avoidance_amd import core
                 gen = dict(f["generate"])
                 scratch = core.BatchedSim(core.make_params(1, f["num_agents"]), device=self.device)
-                f["table"] = scratch.generate_cases(gen.pop("num_cases"), gen.pop("seed"), **gen)
+                if gen.pop("stream", False):   # a case stream: the table held here is episode 0 of THIS batch's envs, row e
+                    gen.pop("window", None)
+                    ids = (torch.arange(E, dtype=torch.int64) + int(f["env_id_offset"])) << 32
+                    f["table"] = scratch.generate_cases_at(ids, gen.pop("seed"), **gen)
+                else:
+                    f["table"] = scratch.generate_cases(gen.pop("num_cases"), gen.pop("seed"), **gen)
                 torch.cuda.synchronize()
-            idx = (f["env_id_offset"] + 0) % len(f["table"])
+            idx = 0 if self._streamed(f) else (f["env_id_offset"] + 0) % len(f["table"])
             row0 = f["table"][idx]
             row0 = row0.cpu().numpy() if hasattr(row0, "cpu") else row0
             row0 = row0[row0[:, 5] > 0]   # (a ragged table pads short cases with radius-0 rows: empty slots)
@@ -381,6 +396,11 @@ class CollisionAvoidanceEnv(Env):
                 agent.max_heading_change = self.max_heading_change
                 agent.max_speed = self.max_speed
         return per_env
+
+    @staticmethod
+    def _streamed(f):
+        """this fixture draws a fresh scenario at every auto-reset (generate=dict(stream=True, ...))"""
+        return bool(f.get("generate") and f["generate"].get("stream"))
 
     def _build_policy_pool(self, f, N):
         """the pool of a policy draw: per entry an agent list of N slots (its policy objects are what the env-0 views hand
@@ -470,6 +490,8 @@ class CollisionAvoidanceEnv(Env):
             tab = self._fixture["table"]
             N = int(tab.shape[1])
             ragged = bool((tab[..., 5] <= 0).any())
+            if self._streamed(self._fixture):   # (later episodes draw their own count, whatever episode 0 drew)
+                ragged = self._fixture["generate"].get("num_agents") is not None
         else:
             lens = [len(g) for g in per_env if g is not None]
             N, ragged = max(lens), len(set(lens)) > 1
@@ -523,8 +545,12 @@ class CollisionAvoidanceEnv(Env):
             if slots is not agents0:
                 self._plugin_ids(agents0)  # leaves self._host_policies describing env 0
             sim.set_plugins(np.array(pol)[None], np.array(dyn)[None], np.array(isl)[None], np.array(stl)[None])
-            sim.set_fixture_table(f["table"] if f["auto_reset"] else None, env_id_offset=f["env_id_offset"],
-                                  case_stride=f["case_stride"], heading_seed=f["heading_seed"])
+            if self._streamed(f):
+                gen = {k_: v for k_, v in f["generate"].items() if k_ != "stream"}
+                sim.set_case_stream(heading_seed=f["heading_seed"], env_id_offset=f["env_id_offset"], **gen)
+            else:
+                sim.set_fixture_table(f["table"] if f["auto_reset"] else None, env_id_offset=f["env_id_offset"],
+                                      case_stride=f["case_stride"], heading_seed=f["heading_seed"])
             if drw is not None:
                 self._policy_pool = self._build_policy_pool(f, N)
                 seed = drw["seed"]
@@ -540,7 +566,7 @@ class CollisionAvoidanceEnv(Env):
                 self._check_log()
                 if sim._log is None:
                     sim.log_episodes(capacity=self._log_capacity())
-            idx = (np.arange(E) + f["env_id_offset"]) % len(f["table"])
+            idx = np.arange(E) if self._streamed(f) else (np.arange(E) + f["env_id_offset"]) % len(f["table"])
             if hasattr(f["table"], "data_ptr"):
                 import torch
                 idx = torch.as_tensor(idx, device=f["table"].device)

@@ -589,6 +589,68 @@ int cagpu_generate_cases_ragged(int64_t num_cases, int32_t max_agents, int32_t n
                                 double radius_lo, double radius_hi, uint64_t seed, double *cases, int32_t *counts,
                                 int32_t *status, void *stream);
 
+/* The same generator at EXPLICIT 64-bit case indices (additive to v12), one WAVE per case: entry m of the list generates
+ * scenario(seed, case_index[m]) -- bit for bit what cagpu_generate_cases / _ragged give that index -- into row out_row[m]
+ * of cases / counts / status.  The arguments are those of cagpu_generate_cases_ragged with num_cases replaced by the list:
+ *   case_index  device int64 [M]: the case indices (the Philox counter takes all 64 bits);
+ *   out_row     device int64 [M] or NULL (row m): where each case lands; the caller keeps the rows inside its table and
+ *               distinct;
+ *   count       device int32 [1] or NULL (M): only the first min(*count, M) entries are processed, read ON THE DEVICE --
+ *               grid and block depend on M only, so a work list built on the device needs no host read-back; the rows of
+ *               the other entries are left alone.
+ * n_max = 0: every case has max_agents agents.  n_ranges = 0: side_ranges is HOST float64 [2] = side lo, hi, the plain form
+ * of cagpu_generate_cases (a draw per case only when hi > lo).  The 64 lanes of a wave evaluate 64 consecutive attempts of
+ * the current agent's rejection loop at once and the first accepted one wins (csrc/cagpu_gen.inc):
+ * fast on a short list, where one thread per case leaves a wave mostly idle.  CA_EINVAL, nothing launched: M outside
+ * 1 .. 2^31 - 1, NULL case_index / cases / side_ranges, max_agents outside 1 .. 1024, n_ranges < 0, and what
+ * cagpu_generate_cases_ragged rejects of the distribution. */
+int cagpu_generate_cases_at(const int64_t *case_index, const int64_t *out_row, const int32_t *count, int64_t M,
+                            int32_t max_agents, int32_t n_min, int32_t n_max, const double *side_ranges, int32_t n_ranges,
+                            double speed_lo, double speed_hi, double radius_lo, double radius_hi, uint64_t seed,
+                            double *cases, int32_t *counts, int32_t *status, void *stream);
+
+/* CASE STREAM (additive to v12; cagpu_stream_refill): a fresh random scenario at EVERY on-device auto-reset -- the batched
+ * form of the reference's default Config.TEST_CASE_FN = "get_testcase_random" (config.py:50-62, test_cases.py:212-253),
+ * which builds a new scenario at every reset() -- without a step kernel knowing: the CaAutoReset's table is a WINDOW of
+ * W upcoming episodes per env that a refill keeps ahead of the envs.
+ * THE RULE, stated once.  With CaAutoReset{table = this table, n_cases = E * W, case_stride = E} the k-th auto-reset of
+ * env e loads row (env_id_offset + e + k * E) % (E * W): slot k % W of env e's own W rows.  Write rc for reset_count[e] as a
+ * refill sees it: after that refill the rows of episodes rc + 1 .. rc + W hold
+ *     scenario(seed, case index = (g << 32) | k),   g = env_id_offset + e (the global env id, required < 2^32), k the episode
+ * -- a pure function of (seed, global env id, episode), whatever the batch size, the sharding, the window or the launch
+ * pattern.  A refill regenerates exactly the slots whose `held` entry differs from the episode they must hold, so it only
+ * ever replaces rows of episodes <= rc.  OVERRUN: an env that auto-resets more than W times between two refills loads a
+ * slot that still holds an older episode -- a repeated scenario, never uninitialised memory; the next refill sees
+ * reset_count[e] - seen[e] > W and raises bit 3 of the fault word (cagpu_device_faults).
+ * reset_obs / reset_plan of the CaAutoReset must be NULL (the rows change under them): the kernels re-sense after an
+ * auto-reset and query the new episode's first action at the start of its step, as with heading_seed != 0 / a policy draw. */
+typedef struct CaCaseStream {
+  double  *table;       /* device [E * W, N, 6]: the window, the table the CaAutoReset points at */
+  int32_t *held;        /* device [E, W]: the episode each window slot holds; the caller initialises it to -1 */
+  int32_t *seen;        /* device [E]: reset_count[e] at the last refill; the caller initialises it to 0 */
+  int64_t *work_index;  /* device [E * W] scratch: the case indices of the stale slots (order unspecified) ...       */
+  int64_t *work_row;    /* device [E * W] scratch: ... and their rows                                               */
+  int32_t *work_count;  /* device [1] scratch: how many (zeroed by every refill)                                      */
+  int32_t *counts;      /* device [E * W] or NULL: the agent count of every row (cagpu_generate_cases_at's counts)   */
+  int32_t *status;      /* device [E * W] or NULL: its status                                                        */
+  int32_t  window;      /* W >= 1 */
+  int32_t  n_min, n_max, n_ranges;   /* the distribution, as cagpu_generate_cases_at takes it */
+  const double *side_ranges;         /* HOST [n_ranges, 4], or [2] with n_ranges = 0 */
+  double   speed_lo, speed_hi, radius_lo, radius_hi;
+  uint64_t seed;
+} CaCaseStream;                      /* 128 bytes */
+
+/* One refill, stream-ordered and without any host synchronisation: a small kernel (one thread per (env, slot)) compares
+ * `held` with the episode each slot must hold, compacts the stale slots into the work list (wave ballot + one atomic per
+ * wave), stamps `held` and `seen` and raises the overrun bit; the wave-per-case generator then runs over the list with the
+ * count read on the device.  Of `s` only reset_count is read.  Call it where the device state is the state last handed
+ * out (ahead of a rollout / ring launch, every W - 1 single steps).  CA_EINVAL, nothing launched: NULL p / s / ar / cs, bad
+ * sizes, NULL reset_count, window < 1, num_envs * window > 2^31 - 1, a NULL pointer among table / held / seen / work_*, a
+ * CaAutoReset that does not name the window (table, n_cases = num_envs * window, case_stride = num_envs) or carries
+ * reset_obs / reset_plan, env_id_offset < 0 or env_id_offset + num_envs > 2^32, and what cagpu_generate_cases_at rejects
+ * of the distribution (num_agents > 1024 included). */
+int cagpu_stream_refill(const CaParams *p, const CaState *s, const CaAutoReset *ar, const CaCaseStream *cs, void *stream);
+
 /* n_steps consecutive cagpu_step calls fused into ONE launch: = CaStepEx{n_steps}. */
 int cagpu_rollout(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions,
                   const CaAutoReset *ar, int32_t n_steps, void *stream);
@@ -727,6 +789,9 @@ uint64_t cagpu_workspace_bytes(const CaParams *p);
  * saturated values.
  * bit 2 = a map-set env's map index (CaMapSet.env_map) lay outside [0, num_maps) (cagpu_step_maps / cagpu_laserscan_maps /
  * cagpu_occupancy_grid_maps, v12): that env saw an empty map in some call since the last clear.
+ * bit 3 = an env of a case stream (CaCaseStream) auto-reset more than `window` times between two refills: it loaded a window
+ * slot that still held an older episode, i.e. it REPEATED a scenario (valid memory, a valid case -- but not the stream's);
+ * raised by cagpu_stream_refill's kernel.  A larger window, or shorter launches, avoid it.
  * *faults receives the word; clear != 0 resets it.  0 in normal operation; check it wherever the host synchronises anyway. */
 int cagpu_device_faults(uint32_t *faults, int32_t clear);
 
