@@ -2596,6 +2596,9 @@ static int laserscan_impl(const CaParams* p, const CaState* s, const CaMap* map,
   if (!s->pos_x || !s->pos_y || !s->heading || !s->radius || !s->step_num) return fail(CA_EINVAL, "cagpu_laserscan: NULL state pointer%s");
   if (!(scan->range_res / map->cell + 0.2 < SCAN_PAD - 1))
     return fail(CA_EUNSUPPORTED, "cagpu_laserscan: range_res above 6 cells is not supported (LDS bitmap border)%s");
+  // (beams are clipped to the grid box + 1 cm, and the march starts up to a sample before that: scan_kernel's `slack`)
+  if (!((scan->range_res + 0.01) / map->cell + 0.2 < SCAN_PAD))
+    return fail(CA_EUNSUPPORTED, "cagpu_laserscan: range_res + 1 cm above 7.8 cells is not supported (LDS bitmap border)%s");
   ScanArgs k;
   std::memset(&k, 0, sizeof(k));
   k.p = *p; k.s = *s; k.m = *map; k.sc = *scan;

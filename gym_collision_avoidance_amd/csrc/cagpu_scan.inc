@@ -221,6 +221,13 @@ __global__ __launch_bounds__(SCAN_NT) void scan_kernel(const ScanArgs k) {
   //     "find the first hit", then "find the next one".
   const int B = k.sc.num_beams, H = k.sc.num_to_store, R = k.sc.num_ranges;
   const float inv_res_f = static_cast<float>(1.0 / k.sc.range_res);
+  // The marched samples start / end `slack` samples before / behind the clipped part [lo, hi] of a beam, so they lie up to
+  // (slack + 1) range_res + 1 cm outside the grid box -- and must stay inside the SCAN_PAD cells of empty border around the
+  // LDS grid, or the march would read what lies behind (the per-agent arrays) or before the grid as cells.  The extra
+  // sample is dropped where it would not fit (range_res above ~3.4 cells): floor / ceil alone leave nearly a whole sample
+  // of safety against the float32 clip, and a sample before lo or behind hi is outside the grid: it can never be a hit.
+  // laserscan_impl admits only geometries whose slack-0 march fits the border.
+  const int slack = ((2.0 * k.sc.range_res + 0.01) * inv_cell + 0.2 < SCAN_PAD) ? 1 : 0;
   // The history (3.): with the reference's 512 beams a round of the loop below is ONE agent; the range indices of HIST_AG
   // agents are staged in LDS (a byte per beam) and the history rows of those agents are then rolled FOUR BEAMS PER THREAD --
   // one dword of range indices per row loaded / stored, one float4 of ranges per row stored -- instead of a byte load, a byte
@@ -236,7 +243,7 @@ __global__ __launch_bounds__(SCAN_NT) void scan_kernel(const ScanArgs k) {
     const double px = a_px[a], py = a_py[a];
     if (a_near[a]) {
       const double sn = b_sn[b] * a_ch[a] + b_cs[b] * a_sh[a], cs = b_cs[b] * a_ch[a] - b_sn[b] * a_sh[a];
-      // the sample indices whose point can lie inside the grid box (conservative: 1 cm box margin, +-1 sample; the
+      // the sample indices whose point can lie inside the grid box (conservative: 1 cm box margin, +-slack samples; the
       // reciprocals need no more than a few digits)
       // (in float32: the box carries a margin of 1 cm and the range +-1 sample, four orders of magnitude above what
       // float32 loses on coordinates of a few tens of metres)
@@ -259,7 +266,7 @@ __global__ __launch_bounds__(SCAN_NT) void scan_kernel(const ScanArgs k) {
         hi = -1.0f;
       }
       if (hi >= lo) {
-        int r_lo = static_cast<int>(floorf(lo * inv_res_f)) - 1, r_hi = static_cast<int>(ceilf(hi * inv_res_f)) + 1;
+        int r_lo = static_cast<int>(floorf(lo * inv_res_f)) - slack, r_hi = static_cast<int>(ceilf(hi * inv_res_f)) + slack;
         r_lo = r_lo < 0 ? 0 : r_lo;
         r_hi = r_hi > R - 1 ? R - 1 : r_hi;
         const int er = static_cast<int>(a_gr[a]) + SCAN_PAD, ec = static_cast<int>(a_gc[a]) + SCAN_PAD;  // padded coordinates

@@ -451,7 +451,10 @@ int cagpu_step_map(const CaParams *p, const CaState *s, const CaOut *o, const do
  * discs into a copy of the static grid held in LDS, every beam is marched through it (the agent's own disc is
  * transparent), the result is the range of the last sample before the SECOND hit (the reference's
  * `cumsum == 1` indexing, LaserScanSensor.py:77-81).  An agent with step_num == 0 takes its first measurement (all
- * history rows filled, :84-85), otherwise the history is rolled (:86-88). */
+ * history rows filled, :84-85), otherwise the history is rolled (:86-88).
+ * CA_EUNSUPPORTED, nothing launched: range_res / cell of 6.8 or more, (range_res + 0.01) / cell of 7.8 or more (the LDS grid
+ * carries 8 cells of empty border, and a beam is marched from up to one sample before the grid box + 1 cm: below these bounds
+ * every sample read lies in the grid or its border, and the indices are the reference's), a map too large for the LDS. */
 int cagpu_laserscan(const CaParams *p, const CaState *s, const CaMap *map, const CaScan *scan, void *stream);
 
 /* cagpu_step_map / cagpu_laserscan with a map set (v12): every env tests its walls against, and scans, its OWN map
