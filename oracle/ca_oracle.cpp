@@ -549,6 +549,23 @@ int ca_oracle_rollout(const OrcParams* p, const OrcState* s, const OrcOut* o, co
 
 void ca_oracle_set_tie_order(int reverse) { orca_ref::g_tie_reverse = reverse ? 1 : 0; }  // (tests only: see orca_ref.h)
 
+// The ORCA stage's linear-programme log (tests only: see orca_ref.h).  _begin clears it and switches it on; _fetch copies up
+// to `cap` per-query entries to `out` (either may be 0 / NULL), the four counters to `counts`, switches it off and returns the
+// number of queries logged.  Bookkeeping only: no velocity depends on it.
+void ca_oracle_lp_log_begin(void) {
+  orca_ref::g_lp_log.clear();
+  for (int i = 0; i < orca_ref::LPC_COUNT; ++i) orca_ref::g_lp_count[i] = 0;
+  orca_ref::g_lp_log_on = 1;
+}
+
+int64_t ca_oracle_lp_log_fetch(int32_t* out, int64_t cap, int64_t* counts /* [4] */) {
+  orca_ref::g_lp_log_on = 0;
+  const int64_t n = static_cast<int64_t>(orca_ref::g_lp_log.size());
+  for (int64_t i = 0; out && i < n && i < cap; ++i) out[i] = orca_ref::g_lp_log[static_cast<size_t>(i)];
+  for (int i = 0; counts && i < orca_ref::LPC_COUNT; ++i) counts[i] = orca_ref::g_lp_count[i];
+  return n;
+}
+
 void ca_oracle_set_libm(double (*atan2_fn)(double, double), void (*sincos_fn)(double, double*, double*)) {
   g_atan2 = atan2_fn;
   g_sincos = sincos_fn;

@@ -127,6 +127,12 @@ int ca_oracle_rollout_ex(const OrcParams* p, const OrcState* s, const OrcOut* o,
  * (NULL = glibc's): lets a test run the oracle on another libm's bits.  Process-wide. */
 void ca_oracle_set_libm(double (*atan2_fn)(double, double), void (*sincos_fn)(double, double*, double*));
 
+/* Tests only: the ORCA stage's linear-programme log (orca_ref.h).  _begin clears it and switches it on; _fetch switches it off,
+ * copies up to cap per-query entries to out (may be NULL) and the four counters to counts (may be NULL), and returns the number
+ * of queries logged.  Process-wide; no result depends on it. */
+void ca_oracle_lp_log_begin(void);
+int64_t ca_oracle_lp_log_fetch(int32_t* out, int64_t cap, int64_t* counts);
+
 /* Stand-alone pieces (same arithmetic as inside step), for per-stage parity tests. */
 /* ORCA: one new velocity per agent from float inputs (rvo2 doStep for every agent of every env). */
 int ca_oracle_orca(int32_t num_envs, int32_t num_agents, const float* pos, const float* vel, const float* pref,

@@ -210,6 +210,15 @@ class Oracle(object):
         assert rc == 0
         return self.obs, self.rewards, self.game_over
 
+    def step_logged(self, ext_actions=None):
+        """step() with the linear-programme log of its ORCA queries -> lp_log_end()'s dict"""
+        lp_log_begin()
+        try:
+            self.step(ext_actions)
+        finally:
+            log = lp_log_end()
+        return log
+
     def set_map(self, static_map=None, rows=160, cols=160, cell=0.1, num_beams=512, num_to_store=3, max_range=6.0,
                 range_res=0.1):
         """Map(16, 16, 0.1) of env.py:389-392 + a LaserScanSensor with its hard-coded parameters
@@ -301,6 +310,38 @@ def set_tie_order(reverse=False):
     L = lib()
     L.ca_oracle_set_tie_order.restype = None
     L.ca_oracle_set_tie_order(C.c_int(1 if reverse else 0))
+
+
+LP_COUNTS = ("collision_lines", "lp1_parallel", "lp1_parallel_reject", "lp3_parallel")
+
+
+def lp_log_begin():
+    """tests only: clear the ORCA stage's linear-programme log (orca_ref.h g_lp_log) and switch it on; process-wide"""
+    L = lib()
+    L.ca_oracle_lp_log_begin.restype = None
+    L.ca_oracle_lp_log_begin()
+
+
+def lp_log_end():
+    """switch the log off and fetch it -> dict: `log` int32 [queries], in query order (env, then agent): -1 = linear programme 2
+    was feasible, else (lines linear programme 3 acted on) + 256 x (lines from the failing one on) + bits 16 .. 30 (which of the
+    later lines acted: the lines after the first acting one, at most 15 positions from the failing line); `queries`, `lp3` (queries
+    that reached linear programme 3), `multi` (those in which two or more LATER lines acted, i.e. at least three lines in all,
+    counted from bits 16 .. 30: a lower bound beyond 15 lines), and the counters LP_COUNTS (half-planes built by the collision branch, |det| <= eps pairs met by linear programme 1,
+    1-D programmes they rejected, parallel / anti-parallel pairs met by linear programme 3)"""
+    L = lib()
+    L.ca_oracle_lp_log_fetch.restype = C.c_int64
+    L.ca_oracle_lp_log_fetch.argtypes = [_I32, C.c_int64, C.POINTER(C.c_int64)]
+    counts = np.zeros(len(LP_COUNTS), np.int64)
+    n = L.ca_oracle_lp_log_fetch(None, 0, None)
+    log = np.zeros(max(int(n), 1), np.int32)
+    L.ca_oracle_lp_log_fetch(_ptr(log, _I32), C.c_int64(int(n)), counts.ctypes.data_as(C.POINTER(C.c_int64)))
+    log = log[:int(n)]
+    acted = np.where(log >= 0, log, 0).astype(np.uint32) >> 16
+    later = sum(((acted >> k) & 1).astype(np.int64) for k in range(15))
+    out = dict(log=log, queries=int(n), lp3=int((log >= 0).sum()), multi=int(((log >= 0) & (later >= 2)).sum()))
+    out.update({k: int(v) for k, v in zip(LP_COUNTS, counts)})
+    return out
 
 
 def round2(x):

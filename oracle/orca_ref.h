@@ -66,6 +66,18 @@ struct Body {  // what one simulated agent carries into a step
 // permutes its agent array, and keeps the permutation from step to step).  tests/test_orca_semantics.py uses it to bound what
 // the visit order of tied neighbours can change at all on the N = 20 / 50 fixtures.
 static int g_tie_reverse = 0;
+// The linear-programme log (tests only, ca_oracle_lp_log_begin / _fetch): bookkeeping beside the arithmetic, never read by it.
+// g_lp_log, per query: number of lines linearProgram3 acted on + 256 x (lines from the failing one on) + bits 16 ..: which later
+// lines acted; -1: linearProgram2 was feasible.  g_lp_count: half-planes built by the collision branch, |det| <= eps pairs met by
+// linearProgram1, linearProgram1 calls those pairs rejected, parallel / anti-parallel pairs met by linearProgram3.
+#ifdef ORCA_REF_STATS
+static int g_lp_log_on = 1;
+#else
+static int g_lp_log_on = 0;
+#endif
+static std::vector<int> g_lp_log;
+enum { LPC_COLLISION_LINES = 0, LPC_LP1_PARALLEL, LPC_LP1_PARALLEL_REJECT, LPC_LP3_PARALLEL, LPC_COUNT };
+static long long g_lp_count[LPC_COUNT];
 static inline void neighbours(const Body* a, size_t n, size_t self, float range_sq, size_t max_nb,
                               std::vector<std::pair<float, size_t> >& out) {
   out.clear();
@@ -116,6 +128,7 @@ static inline HalfPlane half_plane(const Body& me, const Body& ot, float inv_hor
       u = sub(scl(dp2, h.dir), rv);
     }
   } else {  // already overlapping: get out within one time step
+    if (g_lp_log_on) g_lp_count[LPC_COLLISION_LINES] += 1;
     const float inv_dt = 1.0f / time_step;
     const Vec w = sub(rv, scl(inv_dt, rp));
     const float wl = len(w);
@@ -139,7 +152,11 @@ static inline bool lp1(const std::vector<HalfPlane>& L, size_t k, float radius, 
     const float den = cross(L[k].dir, L[i].dir);
     const float num = cross(L[i].dir, sub(L[k].pt, L[i].pt));
     if (std::fabs(den) <= kEps) {
-      if (num < 0.0f) return false;
+      if (g_lp_log_on) g_lp_count[LPC_LP1_PARALLEL] += 1;
+      if (num < 0.0f) {
+        if (g_lp_log_on) g_lp_count[LPC_LP1_PARALLEL_REJECT] += 1;
+        return false;
+      }
       continue;
     }
     const float t = num / den;
@@ -169,7 +186,6 @@ struct LpStats {
 };
 static const float kLpStatsMargins[8] = {0.0f, 0.02f, 0.05f, 0.1f, 0.2f, 0.3f, 0.5f, 1.0f};
 static LpStats g_lp_stats;
-static std::vector<int> g_lp_log;  // per query: number of lines linearProgram3 acted on + 256 x (lines from the failing one on); -1: linearProgram2 was feasible
 #endif
 static inline size_t lp2(const std::vector<HalfPlane>& L, float radius, Vec opt, bool dir_opt, Vec& res) {
   if (dir_opt) res = scl(radius, opt);  // opt * radius (commutative per component)
@@ -238,20 +254,19 @@ static inline size_t lp2(const std::vector<HalfPlane>& L, float radius, Vec opt,
 static inline void lp3(const std::vector<HalfPlane>& L, size_t begin, float radius, Vec& res) {
   float depth = 0.0f;
   std::vector<HalfPlane> P;
-#ifdef ORCA_REF_STATS
-  g_lp_log.push_back(static_cast<int>((L.size() - begin) << 8));  // (bits 8 ..: lines from the failing one on)
-#endif
+  if (g_lp_log_on) g_lp_log.push_back(static_cast<int>((L.size() - begin) << 8));  // (bits 8 ..: lines from the failing one on)
   for (size_t i = begin; i < L.size(); ++i) {
     if (cross(L[i].dir, sub(L[i].pt, res)) > depth) {
-#ifdef ORCA_REF_STATS
-      g_lp_log.back() += 1;
-      if ((g_lp_log.back() & 0xFF) >= 2) g_lp_log.back() |= 1 << (16 + static_cast<int>(i - begin));  // (bits 16 ..: which later lines acted)
-#endif
+      if (g_lp_log_on) {
+        g_lp_log.back() += 1;
+        if ((g_lp_log.back() & 0xFF) >= 2 && i - begin < 15) g_lp_log.back() |= 1 << (16 + static_cast<int>(i - begin));  // (bits 16 .. 30: which later lines acted)
+      }
       P.clear();
       for (size_t j = 0; j < i; ++j) {
         HalfPlane h;
         const float D = cross(L[i].dir, L[j].dir);
         if (std::fabs(D) <= kEps) {
+          if (g_lp_log_on) g_lp_count[LPC_LP3_PARALLEL] += 1;
           if (dot(L[i].dir, L[j].dir) > 0.0f) continue;
           h.pt = scl(0.5f, add(L[i].pt, L[j].pt));
         } else {
@@ -278,9 +293,7 @@ static inline Vec new_velocity(const Body* a, size_t n, size_t self, float neigh
   for (size_t i = 0; i < nb.size(); ++i) L.push_back(half_plane(a[self], a[nb[i].second], inv_h, time_step));
   Vec v;
   const size_t fail = lp2(L, a[self].max_speed, a[self].pref, false, v);
-#ifdef ORCA_REF_STATS
-  if (!(fail < L.size())) g_lp_log.push_back(-1);
-#endif
+  if (g_lp_log_on && !(fail < L.size())) g_lp_log.push_back(-1);
   if (fail < L.size()) lp3(L, fail, a[self].max_speed, v);
   return v;
 }
