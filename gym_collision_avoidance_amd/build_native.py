@@ -14,15 +14,18 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wn
          "-I" + os.path.join(REPO, "include")]
 
 
+def source_files():
+    """everything the library is compiled from, in a fixed order: all of csrc/ + the header.  A new include of cagpu.hip
+    (cagpu_render.inc and cagpu_rules.inc were the last two) is a dependency of the build without being named here."""
+    csrc = os.path.join(HERE, "csrc")
+    return [os.path.join(csrc, f) for f in sorted(os.listdir(csrc))] + [os.path.join(REPO, "include", "cagpu.h")]
+
+
 def needs_build():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = [SRC, os.path.join(HERE, "csrc", "cagpu_grouplp.inc"), os.path.join(HERE, "csrc", "cagpu_scan.inc"),
-            os.path.join(HERE, "csrc", "cagpu_occ.inc"), os.path.join(HERE, "csrc", "cagpu_render.inc"),
-            os.path.join(HERE, "csrc", "cagpu_ga3c.inc"), os.path.join(HERE, "csrc", "cagpu_gen.inc"), os.path.join(HERE, "csrc", "cagpu_pipe.inc"), os.path.join(HERE, "csrc", "cagpu_big.inc"),
-            os.path.join(REPO, "include", "cagpu.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in source_files())
 
 
 def build(force=False, verbose=False, variant=None):
@@ -64,8 +67,7 @@ def source_digest():
     """sha256 over the kernel sources + the header, in a fixed order: names the source tree a library was built from"""
     import hashlib
     h = hashlib.sha256()
-    for f in sorted(os.listdir(os.path.join(HERE, "csrc"))) + [os.path.join(REPO, "include", "cagpu.h")]:
-        path = f if os.path.isabs(f) else os.path.join(HERE, "csrc", f)
+    for path in source_files():
         h.update(os.path.basename(path).encode() + b"\0" + open(path, "rb").read())
     return h.hexdigest()
 

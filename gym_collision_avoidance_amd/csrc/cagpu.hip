@@ -798,6 +798,8 @@ __device__ __forceinline__ void reset_lane(Lane& r, const double* c, const bool 
   }
 }
 
+#include "cagpu_rules.inc"
+
 template <int NT, bool STAGE, int NC, bool MULTI, bool RO, int TE = 0>
 // n-step: <= 128 VGPRs (four 4-wave workgroups per CU) -- except N = 20, whose single-step form already needs 172 (two
 // workgroups per CU either way): held to 128 its n-step form spilled ~200 VGPRs to scratch around the step loop
@@ -1233,20 +1235,7 @@ LP1_UNROLL
         if (query) {
           if (pol == CA_POL_RVO) {
             const float ts = static_cast<float>(p.rvo_dt);
-            const F2 v = v_orca;
-            // Agent::update: float position += v * timeStep; RVOPolicy.py:96-111
-            const float npx = sh_fpx[lane] + v.x * ts, npy = sh_fpy[lane] + v.y * ts;
-            const double dpx = static_cast<double>(npx) - r.px, dpy = static_cast<double>(npy) - r.py;
-            const double ang = AB(4) ? dpy : atan2(dpy, dpx);
-            TICK(13);
-            const double nh = (ang < 0.0) ? ang + kTwoPi : ((ang == 0.0) ? 0.0 : ang);  // `% (2*pi)`, :102
-            dh = wrap_pi(nh - r.heading);
-            TICK(14);
-            spd = k.inv_rvo_dt * sqrtd(dpx * dpx + dpy * dpy);  // RVOPolicy.py:106: 1/self.dt * norm
-            if (fabs(dh) > kPi / 6) {
-              dh = ((dh > 0.0) - (dh < 0.0)) * (kPi / 6);
-              spd = 0.0;
-            }
+            rvo_action(sh_fpx[lane], sh_fpy[lane], v_orca, ts, r.px, r.py, r.heading, k.inv_rvo_dt, spd, dh);
             if (k.s.rvo_heading_noise) dh = dh + k.s.rvo_heading_noise[i];  // RVOPolicy.py:118-119 (drawn by the caller)
           } else if (pol == CA_POL_NONCOOP) {  // NonCooperativePolicy.py:21
             const Ego eg = ego_frame(r.px, r.py, r.gx, r.gy, r.heading);
@@ -1257,22 +1246,7 @@ LP1_UNROLL
             r.gy = r.py;
             statics_dirty = true;
           } else if (k.ext) {
-            const double e0 = k.ext[2 * i], e1 = k.ext[2 * i + 1];
-            if (pol == CA_POL_EXTERNAL) {  // ExternalPolicy.py:14-16
-              spd = e0;
-              dh = e1;
-            } else if (pol == CA_POL_LEARNING) {  // LearningPolicy.py:29-33
-              dh = p.max_heading_change * (2. * e1 - 1.);
-              spd = r.ps * e0;
-            } else if (pol == CA_POL_LEARNING_GA3C || pol == CA_POL_GA3C_CADRL) {  // LearningPolicyGA3C.py:24-26,
-              // GA3CCADRLPolicy.py:81-84 (index from cagpu_ga3c), network.py:7-16
-              int q = static_cast<int>(e0);
-              q = q < 0 ? 0 : (q > 10 ? 10 : q);
-              const int hq = (q < 5) ? q - 2 : ((q - 5) % 3 - 1) * 2;  // heading index in units of pi/12
-              const double s0 = (q < 5) ? 1.0 : ((q < 8) ? 0.5 : 0.0);
-              spd = r.ps * s0;
-              dh = (hq == -2) ? -kPi / 6 : (hq == -1) ? -kPi / 12 : (hq == 0) ? 0.0 : (hq == 1) ? kPi / 12 : kPi / 6;
-            }
+            ext_policy_action(pol, k.ext[2 * i], k.ext[2 * i + 1], r.ps, p.max_heading_change, spd, dh);
           }
         }
         TICK(4);
@@ -1280,53 +1254,11 @@ LP1_UNROLL
         if (active && k.o.actions) reinterpret_cast<float2*>(k.o.actions)[i + ring_a] = make_float2(a0f, a1f);
         if (active && k.o.orca_vel)  // parity hook: the velocity rvo2 chose for this agent (RVOPolicy.py:93), 0 if not queried
           reinterpret_cast<float2*>(k.o.orca_vel)[i + ring_a] = rvo ? make_float2(v_orca.x, v_orca.y) : make_float2(0.f, 0.f);
-        // trajectory tape (CaTraj): who moves is known before the move, and the row's clock is the one BEFORE its increment:
-        // stored here, so that nothing but one predicate lives across the move for the rest of the row
+        // trajectory tape (CaTraj): who moves (move_lane's done gate) is known before the move, and the row's clock is the one
+        // BEFORE its increment: stored here, so that nothing but one predicate lives across the move for the rest of the row
         const bool moved = active && !(r.flags & (CA_AT_GOAL | CA_OUT_OF_TIME | CA_IN_COLLISION));
         if (k.traj_rows && moved) k.traj_rows[(i + traj_a) * 12] = r.t;
-        if (active) {
-          if (r.flags & (CA_AT_GOAL | CA_OUT_OF_TIME | CA_IN_COLLISION)) {
-            if (r.flags & CA_AT_GOAL) r.flags |= CA_WAS_AT_GOAL;
-            if (r.flags & CA_IN_COLLISION) r.flags |= CA_WAS_IN_COLLISION;
-            r.vx = r.vy = 0.0;
-          } else {
-            r.act0 = a0f;
-            r.act1 = a1f;
-            const double a0 = a0f, a1 = a1f;
-            const uint32_t dyn = (r.flags >> CA_DYNAMICS_SHIFT) & 0xF;
-            if (dyn != CA_DYN_EXTERNAL) {
-              double nh;
-              if (dyn == CA_DYN_MAX_TURN_RATE) {  // UnicycleDynamicsMaxTurnRate.py:31-33
-                double trn = a1 / p.dt;
-                trn = fmin(fmax(trn, -3.0), 3.0);
-                nh = wrap_pi(trn * p.dt + r.heading);
-              } else {
-                nh = wrap_pi(a1 + r.heading);  // UnicycleDynamics.py:28
-              }
-              double sn, cs;
-              if (AB(8)) { sn = nh; cs = 1.0 - nh; } else sincos_heading(nh, sn, cs);
-              r.px += a0 * cs * p.dt;
-              r.py += a0 * sn * p.dt;
-              r.vx = a0 * cs;
-              r.vy = a0 * sn;
-              r.heading = nh;
-              if (dyn == CA_DYN_UNICYCLE) r.td = turning_dir_next(r.td, nh);
-            } else if (k.s.ext_state) {  // a host-side Dynamics subclass integrated this agent (agent.py:214-220)
-              const double* q = k.s.ext_state + 5 * i;
-              const double npx = q[0], npy = q[1], nvx = q[2], nvy = q[3], nh = q[4];
-              if (!(npx != npx || npy != npy || nvx != nvx || nvy != nvy || nh != nh)) {
-                r.px = npx; r.py = npy; r.vx = nvx; r.vy = nvy; r.heading = nh;
-              }
-            }
-            const double qx = r.px - r.gx, qy = r.py - r.gy;
-            if (qx * qx + qy * qy <= p.near_goal_threshold * p.near_goal_threshold) r.flags |= CA_AT_GOAL;
-            else r.flags &= ~static_cast<uint32_t>(CA_AT_GOAL);
-            r.tr -= p.dt;
-            r.t += p.dt;
-            r.step_num += 1;
-            if (r.tr <= 0.0) r.flags |= CA_OUT_OF_TIME;
-          }
-        }
+        if (active) move_lane(r, a0f, a1f, p, k.s.ext_state, i);
         if (k.traj_rows && active) {  // trajectory tape (CaTraj): after the move, before any auto-reset of this step
           double* row = k.traj_rows + (i + traj_a) * 12;
           if (moved) traj_store_tail(row, r.px, r.py, r.gx, r.gy, r.rad, r.ps, r.vx, r.vy, r.act0, r.heading, r.step_num - 1);
@@ -1610,12 +1542,7 @@ LP1_UNROLL
         }
         if (do_sense) {
           float* row = (STAGE ? sh_obs : obs_tile) + __mul24(lane, W);
-          const bool here = !(p.ragged && (r.flags & CA_ABSENT));
-          row[0] = (here && (r.flags & CA_IS_LEARNING)) ? 1.f : 0.f;
-          row[2] = here ? static_cast<float>(eg.dist) : 0.f;
-          row[3] = here ? static_cast<float>(eg.heading_ego) : 0.f;
-          row[4] = here ? static_cast<float>(r.ps) : 0.f;
-          row[5] = static_cast<float>(r.rad);
+          obs_own_columns(row, !(p.ragged && (r.flags & CA_ABSENT)), r.flags, eg.dist, eg.heading_ego, r.ps, r.rad);
         }
       }
 
@@ -1632,7 +1559,7 @@ LP1_UNROLL
         if (wave0 && active) {
           // AND / OR of the env's flag words, then bit tests: no short-circuit chains (they compile to one dependent
           // LDS round trip + branch per agent)
-          uint32_t f_and = ~0u, f_or = 0u, learn_and = ~0u;
+          uint32_t f_and = ~0u, f_or = 0u, learn_and = ~0u;  // (FlagFold of cagpu_rules.inc, in this kernel's own text)
           for_n<8>(N, [&](const int j) {
             const uint32_t f = sh_flag[ebase + j];
             f_and &= f;
@@ -1655,24 +1582,11 @@ LP1_UNROLL
                 ttg += sh_r1[ebase + j];
                 extra += sh_r2[ebase + j];
               });
-              double* st = k.s.env_stats + 8 * e;
-              st[0] += 1.0;
-              if (any_coll) st[1] += 1.0;
-              else if (all_goal) st[2] += 1.0;
-              else st[3] += 1.0;
-              st[4] += ep_step;
-              st[5] += tot_r;
-              st[6] += ttg;
-              st[7] += extra;
+              env_stats_add(k.s.env_stats + 8 * e, any_coll, all_goal, ep_step, tot_r, ttg, extra);
             }
             reset_cnt += 1;
-            const long c = (k.env_id_offset + e + static_cast<long>(reset_cnt) * k.case_stride) % k.n_cases;
-            double h0 = 0.0;
-            if (k.heading_seed) {  // test_cases.py:558-559 (training mode): uniform in [-pi, pi)
-              const unsigned long long ge = static_cast<unsigned long long>(k.env_id_offset + e);
-              h0 = -kPi + kTwoPi * gen::uniform_at(k.heading_seed, static_cast<unsigned>(ge), static_cast<unsigned>(ge >> 32),
-                                                   static_cast<unsigned>(reset_cnt), static_cast<unsigned>(a));
-            }
+            const long c = reset_case(k, e, reset_cnt);
+            const double h0 = reset_heading(k, e, reset_cnt, a);
             if (k.fin_flags) k.fin_flags[i + ring_a] = r.flags;  // final record (CaFinal): the terminal step's flag word
             // episode log (CaEpLog): the three addends of this lane, its flag word and -- agent 0 -- the episode's head
             if (k.log_rows)

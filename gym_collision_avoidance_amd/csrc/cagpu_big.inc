@@ -108,18 +108,7 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
           v_orca = orca_velocity<NT>(sh_fpx, sh_fpy, sh_fvx, sh_fvy, sh_frad, 0, a, N, pref, static_cast<float>(r.ps), collab,
                                      static_cast<float>(p.rvo_time_horizon), static_cast<float>(p.rvo_dt),
                                      static_cast<float>(p.sensing_horizon), p.rvo_max_neighbors, fcol, Lcol, Pcol);
-          const float ts = static_cast<float>(p.rvo_dt);
-          // Agent::update: float position += v * timeStep; RVOPolicy.py:96-111
-          const float npx = sh_fpx[a] + v_orca.x * ts, npy = sh_fpy[a] + v_orca.y * ts;
-          const double dpx = static_cast<double>(npx) - r.px, dpy = static_cast<double>(npy) - r.py;
-          const double ang = atan2(dpy, dpx);
-          const double nh = (ang < 0.0) ? ang + kTwoPi : ((ang == 0.0) ? 0.0 : ang);  // `% (2*pi)`, :102
-          dh = wrap_pi(nh - r.heading);
-          spd = k.inv_rvo_dt * sqrtd(dpx * dpx + dpy * dpy);  // :106
-          if (fabs(dh) > kPi / 6) {
-            dh = ((dh > 0.0) - (dh < 0.0)) * (kPi / 6);
-            spd = 0.0;
-          }
+          rvo_action(sh_fpx[a], sh_fpy[a], v_orca, static_cast<float>(p.rvo_dt), r.px, r.py, r.heading, k.inv_rvo_dt, spd, dh);
           if (k.s.rvo_heading_noise) dh = dh + k.s.rvo_heading_noise[i];  // :118-119 (drawn by the caller)
         } else if (pol == CA_POL_NONCOOP) {  // NonCooperativePolicy.py:21
           const Ego eg = ego_frame(r.px, r.py, r.gx, r.gy, r.heading);
@@ -130,21 +119,7 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
           r.gy = r.py;
           statics_dirty = true;
         } else if (k.ext) {
-          const double e0 = k.ext[2 * i], e1 = k.ext[2 * i + 1];
-          if (pol == CA_POL_EXTERNAL) {  // ExternalPolicy.py:14-16
-            spd = e0;
-            dh = e1;
-          } else if (pol == CA_POL_LEARNING) {  // LearningPolicy.py:29-33
-            dh = p.max_heading_change * (2. * e1 - 1.);
-            spd = r.ps * e0;
-          } else if (pol == CA_POL_LEARNING_GA3C || pol == CA_POL_GA3C_CADRL) {  // LearningPolicyGA3C.py:24-26
-            int q = static_cast<int>(e0);
-            q = q < 0 ? 0 : (q > 10 ? 10 : q);
-            const int hq = (q < 5) ? q - 2 : ((q - 5) % 3 - 1) * 2;  // heading index in units of pi/12
-            const double s0 = (q < 5) ? 1.0 : ((q < 8) ? 0.5 : 0.0);
-            spd = r.ps * s0;
-            dh = (hq == -2) ? -kPi / 6 : (hq == -1) ? -kPi / 12 : (hq == 0) ? 0.0 : (hq == 1) ? kPi / 12 : kPi / 6;
-          }
+          ext_policy_action(pol, k.ext[2 * i], k.ext[2 * i + 1], r.ps, p.max_heading_change, spd, dh);
         }
       }
       const float a0f = static_cast<float>(spd), a1f = static_cast<float>(dh);  // float32 `all_actions`
@@ -154,51 +129,7 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
       // ================= move (Agent.take_action, agent.py:192-241)
       const double t_pre = r.t;         // (the trajectory row holds the clock and the index BEFORE their increments)
       const int index_pre = r.step_num;
-      bool moved = false;
-      if (active) {
-        if (r.flags & (CA_AT_GOAL | CA_OUT_OF_TIME | CA_IN_COLLISION)) {
-          if (r.flags & CA_AT_GOAL) r.flags |= CA_WAS_AT_GOAL;
-          if (r.flags & CA_IN_COLLISION) r.flags |= CA_WAS_IN_COLLISION;
-          r.vx = r.vy = 0.0;
-        } else {
-          moved = true;
-          r.act0 = a0f;
-          r.act1 = a1f;
-          const double a0 = a0f, a1 = a1f;
-          const uint32_t dyn = (r.flags >> CA_DYNAMICS_SHIFT) & 0xF;
-          if (dyn != CA_DYN_EXTERNAL) {
-            double nh;
-            if (dyn == CA_DYN_MAX_TURN_RATE) {  // UnicycleDynamicsMaxTurnRate.py:31-33
-              double trn = a1 / p.dt;
-              trn = fmin(fmax(trn, -3.0), 3.0);
-              nh = wrap_pi(trn * p.dt + r.heading);
-            } else {
-              nh = wrap_pi(a1 + r.heading);  // UnicycleDynamics.py:28
-            }
-            double sn, cs;
-            sincos_heading(nh, sn, cs);
-            r.px += a0 * cs * p.dt;
-            r.py += a0 * sn * p.dt;
-            r.vx = a0 * cs;
-            r.vy = a0 * sn;
-            r.heading = nh;
-            if (dyn == CA_DYN_UNICYCLE) r.td = turning_dir_next(r.td, nh);
-          } else if (k.s.ext_state) {  // a host-side Dynamics subclass integrated this agent (agent.py:214-220)
-            const double* q = k.s.ext_state + 5 * i;
-            const double npx = q[0], npy = q[1], nvx = q[2], nvy = q[3], nh = q[4];
-            if (!(npx != npx || npy != npy || nvx != nvx || nvy != nvy || nh != nh)) {
-              r.px = npx; r.py = npy; r.vx = nvx; r.vy = nvy; r.heading = nh;
-            }
-          }
-          const double qx = r.px - r.gx, qy = r.py - r.gy;
-          if (qx * qx + qy * qy <= p.near_goal_threshold * p.near_goal_threshold) r.flags |= CA_AT_GOAL;
-          else r.flags &= ~static_cast<uint32_t>(CA_AT_GOAL);
-          r.tr -= p.dt;
-          r.t += p.dt;
-          r.step_num += 1;
-          if (r.tr <= 0.0) r.flags |= CA_OUT_OF_TIME;
-        }
-      }
+      const bool moved = active && move_lane(r, a0f, a1f, p, k.s.ext_state, i);
       if (k.traj_rows && active) {  // trajectory tape (CaTraj): after the move, before any auto-reset of this step
         double* row = k.traj_rows + i * 12;   // (one launch per step: the host advances the slot)
         if (moved) traj_store(row, t_pre, r.px, r.py, r.gx, r.gy, r.rad, r.ps, r.vx, r.vy, r.act0, r.heading, index_pre);
@@ -277,12 +208,8 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
       if (do_sense) {
         float* row = k.o.obs + i * W;
         const int keep = cnt < p.obs_clip ? cnt : p.obs_clip;  // sensor :39
-        row[0] = (here && (r.flags & CA_IS_LEARNING)) ? 1.f : 0.f;
+        obs_own_columns(row, here, r.flags, eg.dist, eg.heading_ego, r.ps, sh_rad[a]);
         row[1] = static_cast<float>(keep);
-        row[2] = here ? static_cast<float>(eg.dist) : 0.f;
-        row[3] = here ? static_cast<float>(eg.heading_ego) : 0.f;
-        row[4] = here ? static_cast<float>(r.ps) : 0.f;
-        row[5] = static_cast<float>(sh_rad[a]);
         for (int sl = keep; sl < K; ++sl) {  // zero the unfilled rows (sensor :112)
           float* z = row + 6 + 7 * sl;
           z[0] = z[1] = z[2] = z[3] = z[4] = z[5] = z[6] = 0.f;
@@ -348,18 +275,10 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
       sh_flag[a] = active ? r.flags : (CA_DONE | CA_AT_GOAL | CA_ABSENT);
       sh_r0[a] = r.epr; sh_r1[a] = r.t; sh_r2[a] = r.t - r.slt;
       __syncthreads();
-      uint32_t f_and = ~0u, f_or = 0u, learn_and = ~0u;
-      for (int j = 0; j < N; ++j) {
-        const uint32_t f = sh_flag[j];
-        f_and &= f;
-        f_or |= f;
-        learn_and &= (f & CA_STILL_LEARNING) ? f : ~0u;  // learners only
-      }
-      const bool all_done = (f_and & CA_DONE) != 0, all_learning_done = (learn_and & CA_DONE) != 0;
-      const bool any_coll = (f_or & CA_IN_COLLISION) != 0, all_goal = (f_and & CA_AT_GOAL) != 0;
-      bool over = all_done;
-      if (p.game_over_mode == CA_OVER_AGENT0) over = (sh_flag[0] & CA_DONE) != 0;
-      else if (p.game_over_mode == CA_OVER_LEARNING_DONE) over = all_learning_done;
+      FlagFold fold;
+      for (int j = 0; j < N; ++j) fold.add(sh_flag[j]);
+      const bool any_coll = fold.any_coll(), all_goal = fold.all_goal();
+      const bool over = fold.over(p.game_over_mode, sh_flag[0]);
       if (active) {
         k.o.rewards[i] = reward;
         k.o.done[i] = static_cast<uint8_t>((r.flags & CA_DONE) != 0);
@@ -373,20 +292,12 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
           ttg += sh_r1[j];
           extra += sh_r2[j];
         }
-        double* st = k.s.env_stats + 8 * e;
-        st[0] += 1.0;
-        if (any_coll) st[1] += 1.0;
-        else if (all_goal) st[2] += 1.0;
-        else st[3] += 1.0;
-        st[4] += ep_step;
-        st[5] += tot_r;
-        st[6] += ttg;
-        st[7] += extra;
+        env_stats_add(k.s.env_stats + 8 * e, any_coll, all_goal, ep_step, tot_r, ttg, extra);
       }
       reset_cnt += 1;
       // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by agent 0's thread
       if (k.map_seed && a == 0) k.env_map[e] = map_draw(k.map_seed, k.env_id_offset + e, reset_cnt, k.num_maps);
-      const long c = (k.env_id_offset + e + static_cast<long>(reset_cnt) * k.case_stride) % k.n_cases;
+      const long c = reset_case(k, e, reset_cnt);
       // policy draw (CaPolicyDraw; workgroup-uniform like the branch it sits on): every thread draws its own slot's pool
       // index once and the env settles the ensure rule through sh_flag (free again: every thread has read the flag words)
       int drawn = -1;
@@ -409,12 +320,7 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
         }
       }
       if (active) {
-        double h0 = 0.0;
-        if (k.heading_seed) {  // test_cases.py:558-559 (training mode): uniform in [-pi, pi)
-          const unsigned long long ge = static_cast<unsigned long long>(k.env_id_offset + e);
-          h0 = -kPi + kTwoPi * gen::uniform_at(k.heading_seed, static_cast<unsigned>(ge), static_cast<unsigned>(ge >> 32),
-                                               static_cast<unsigned>(reset_cnt), static_cast<unsigned>(a));
-        }
+        const double h0 = reset_heading(k, e, reset_cnt, a);
         if (k.fin_obs) {  // final record (CaFinal): this thread's own terminal row and flag word, before the second pass
           const float* src = k.o.obs + i * W;   // (one launch per step: the host advances the block with the outputs)
           float* dst = k.fin_obs + i * W;

@@ -650,21 +650,8 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
               gx_m = px; gy_m = py;
               statics_dirty = true;
             } else if (k.ext) {
-              const double e0 = (k.ext + 2 * tile_base)[2 * lane], e1 = (k.ext + 2 * tile_base)[2 * lane + 1];
-              if (pol_ == CA_POL_EXTERNAL) {  // ExternalPolicy.py:14-16
-                spd = e0;
-                dh = e1;
-              } else if (pol_ == CA_POL_LEARNING) {  // LearningPolicy.py:29-33
-                dh = p.max_heading_change * (2. * e1 - 1.);
-                spd = sh_ps[lane] * e0;
-              } else if (pol_ == CA_POL_LEARNING_GA3C || pol_ == CA_POL_GA3C_CADRL) {  // LearningPolicyGA3C.py:24-26
-                int q = static_cast<int>(e0);
-                q = q < 0 ? 0 : (q > 10 ? 10 : q);
-                const int hq = (q < 5) ? q - 2 : ((q - 5) % 3 - 1) * 2;  // heading index in units of pi/12
-                const double s0 = (q < 5) ? 1.0 : ((q < 8) ? 0.5 : 0.0);
-                spd = sh_ps[lane] * s0;
-                dh = (hq == -2) ? -kPi / 6 : (hq == -1) ? -kPi / 12 : (hq == 0) ? 0.0 : (hq == 1) ? kPi / 12 : kPi / 6;
-              }
+              ext_policy_action(pol_, (k.ext + 2 * tile_base)[2 * lane], (k.ext + 2 * tile_base)[2 * lane + 1], sh_ps[lane],
+                                p.max_heading_change, spd, dh);
             }
             a0f = static_cast<float>(spd);  // float32 `all_actions`
             a1f = static_cast<float>(dh);
@@ -803,7 +790,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         if (d) flags |= CA_DONE; else flags &= ~static_cast<uint32_t>(CA_DONE);
         sh_flag[lane] = flags;
         sh_r2[lane] = sh_t[lane] - sh_slt[lane];
-        float* row = obs_tile + __mul24(lane, W);
+        float* row = obs_tile + __mul24(lane, W);  // (obs_own_columns of cagpu_rules.inc, in this kernel's own text)
         row[0] = (here && (flags & CA_IS_LEARNING)) ? 1.f : 0.f;
         row[2] = here ? static_cast<float>(eg_dist) : 0.f;
         row[3] = here ? static_cast<float>(eg_hego) : 0.f;
@@ -817,7 +804,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
       {
         bool reset_here = false;
         if (active) {
-          uint32_t f_and = ~0u, f_or = 0u, learn_and = ~0u;
+          uint32_t f_and = ~0u, f_or = 0u, learn_and = ~0u;  // (FlagFold of cagpu_rules.inc, in this kernel's own text)
 #pragma unroll
           for (int j = 0; j < N; ++j) {
             const uint32_t f = sh_flag[ebase + j];
@@ -843,15 +830,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
                 ttg += sh_r1[ebase + j];
                 extra += sh_r2[ebase + j];
               }
-              double* st = k.s.env_stats + 8 * env0 + 8 * le;
-              st[0] += 1.0;
-              if (any_coll) st[1] += 1.0;
-              else if (all_goal) st[2] += 1.0;
-              else st[3] += 1.0;
-              st[4] += ep_step;
-              st[5] += tot_r;
-              st[6] += ttg;
-              st[7] += extra;
+              env_stats_add(k.s.env_stats + 8 * env0 + 8 * le, any_coll, all_goal, ep_step, tot_r, ttg, extra);
             }
             reset_here = true;
           }
@@ -859,6 +838,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
           __builtin_amdgcn_wave_barrier();
           if (reset_here) {
             reset_cnt += 1;
+            // (reset_case of cagpu_rules.inc, in this kernel's own text)
             const long c = (k.env_id_offset + env0 + le + static_cast<long>(reset_cnt) * k.case_stride) % k.n_cases;
             // final record (CaFinal): the flag word as the terminal step leaves it, in the slot of this step's outputs
             if (FINAL && k.fin_flags) (k.fin_flags + out_base)[lane] = flags;
@@ -1395,6 +1375,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         float4 pl = make_float4(0.f, 0.f, 0.f, 0.f);
         PIPE_DUP(32, v_orca.x)
         if (isq) {
+          // (rvo_action of cagpu_rules.inc, in this kernel's own text: the call changes its instructions)
           const float tsf = static_cast<float>(p.rvo_dt);
           const double px = sh_px[lane], py = sh_py[lane];
           const float npx = sh_fpx[lane] + v_orca.x * tsf, npy = sh_fpy[lane] + v_orca.y * tsf;

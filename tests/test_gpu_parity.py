@@ -1528,20 +1528,27 @@ def test_rvo_stochastic_batch_statistics():
     assert nat.lib().cagpu_last_kernel().decode().startswith("ca_pipe_kernel<10, 4")
 
 
-def test_ext_state_applied_at_the_move_vs_oracle():
+# (N = 65, E = 2: the smallest shape of the large-env kernel, which shares the move with ca_kernel but hands it its own
+# index and pointers; 130 agents, 40 % external, 70 % moved: 36 expected takers)
+@pytest.mark.parametrize("N,E,kernel,min_took", [(6, 120, "ca_kernel<", 50), (65, 2, "ca_big_kernel", 10)])
+def test_ext_state_applied_at_the_move_vs_oracle(N, E, kernel, min_took):
     """CaState.ext_state: agents with ExternalDynamics take an externally integrated state AT THE MOVE of the step -- after
     every policy has seen the pre-step state, before at-goal / clocks / collisions / sensing -- NaN rows and agents with
     built-in dynamics ignore it; kernel and oracle agree (re-injected)"""
     nat, core, orc = _mods()
-    N, E = 6, 120
     rng = np.random.default_rng(9)
-    table = gu.fixtures(N)
+    if N <= 64:
+        table = gu.fixtures(N)
+    else:
+        from gym_collision_avoidance_amd.envs import test_cases as tc
+        np.random.seed(N)
+        table = tc.make_testcase_huge(E, N, side_length=2.0 * np.sqrt(N) + 3.0, speed_bnds=[0.5, 1.5], radius_bnds=[0.2, 0.5])
     o, g = _pair(E, N)
     pol = np.where(rng.random((E, N)) < 0.6, orc.POL_RVO, orc.POL_NONCOOP).astype(np.int32)
     dyn = np.where(rng.random((E, N)) < 0.4, orc.DYN_EXTERNAL, orc.DYN_UNICYCLE).astype(np.int32)
     o.set_policies(pol, dyn)
     g.set_plugins(pol, dyn)
-    o.reset(table[np.arange(E) % 500])
+    o.reset(table[np.arange(E) % table.shape[0]])
     for _ in range(15):
         o.step()
     for t in range(12):
@@ -1553,10 +1560,10 @@ def test_ext_state_applied_at_the_move_vs_oracle():
         _upload(o, g)
         o.step()
         g.step(ext_state=st)
-        assert nat.lib().cagpu_last_kernel().decode().startswith("ca_kernel<")
+        assert nat.lib().cagpu_last_kernel().decode().startswith(kernel)
         _compare(o, g, what="ext_state step %d" % t)
     took = (dyn == orc.DYN_EXTERNAL) & move & ((o.view("flags") & (orc.AT_GOAL | orc.OUT_OF_TIME | orc.IN_COLLISION)) == 0)
-    assert took.sum() > 50
+    assert took.sum() > min_took
     np.testing.assert_allclose(g.state["pos_x"].cpu().numpy()[took], st[..., 0][took], rtol=0, atol=1e-12)
     g.step()            # without ext_state again: the pointer is cleared
     assert g._cs.ext_state is None or not g._cs.ext_state
@@ -1584,7 +1591,7 @@ def test_big_envs_vs_oracle(N, E, K, sort, ragged):
     o, g = _pair(E, N, K, sort_mode=sort, ragged=ragged, max_time_ratio=mtr, game_over_mode=1)
     assert g._workspace is not None and g._workspace.numel() == int(nat.lib().cagpu_workspace_bytes(g.p))
     pol = rng.choice([orc.POL_RVO, orc.POL_RVO, orc.POL_RVO, orc.POL_NONCOOP, orc.POL_STATIC, orc.POL_EXTERNAL,
-                      orc.POL_LEARNING], (E, N)).astype(np.int32)
+                      orc.POL_LEARNING, orc.POL_LEARNING_GA3C], (E, N)).astype(np.int32)
     dyn = rng.choice([orc.DYN_UNICYCLE, orc.DYN_UNICYCLE, orc.DYN_MAX_TURN_RATE], (E, N)).astype(np.int32)
     o.set_policies(pol, dyn)
     g.set_plugins(pol, dyn)
@@ -1596,6 +1603,8 @@ def test_big_envs_vs_oracle(N, E, K, sort, ragged):
     ended = 0
     for t in range(45):
         ext = rng.uniform(0.0, 1.0, (E, N, 2))
+        # (LearningPolicyGA3C reads an action index: all eleven, and one beyond either end for the clamp)
+        ext[..., 0] = np.where(pol == orc.POL_LEARNING_GA3C, rng.integers(-1, 12, (E, N)), ext[..., 0])
         _upload(o, g)
         o.rollout_ex(table, 1, ext_actions=ext)
         g.step(ext)
