@@ -85,6 +85,12 @@ class CaEpLog(C.Structure):
     _fields_ = [("rows", _P), ("head", _P), ("capacity", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class CaEpMetrics(C.Structure):
+    """the episode metrics' records, ring and carry (cagpu_episode_metrics); include/cagpu.h states the rules"""
+    _fields_ = [("vals", _P), ("cnts", _P), ("head", _P), ("capacity", C.c_int32), ("reserved0", C.c_int32), ("carry", _P),
+                ("getting_close_range", C.c_double)]
+
+
 class CaStepEx(C.Structure):
     """one step / rollout launch (cagpu_step_ex).  The five record pointers are plain addresses (C.addressof of a CaMap /
     CaMapSet / CaTraj / CaFinal / CaEpLog, None = not used): whoever stores one keeps that struct alive"""
@@ -145,7 +151,7 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_step_traj", "cagpu_rollout_traj", "cagpu_step_final", "cagpu_rollout_final",
            "cagpu_step_log", "cagpu_rollout_log", "cagpu_step_ex", "cagpu_step_draw", "cagpu_policy_draw",
            "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes", "cagpu_ga3c_query", "cagpu_ga3c_value",
-           "cagpu_generate_cases_at", "cagpu_stream_refill")
+           "cagpu_generate_cases_at", "cagpu_stream_refill", "cagpu_episode_metrics_carry_bytes", "cagpu_episode_metrics")
 
 _lib = None
 
@@ -212,6 +218,9 @@ def lib():
     L.cagpu_generate_cases_at.argtypes = ([_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32] +
                                           [C.c_double] * 4 + [C.c_uint64, _P, _P, _P, _P])
     L.cagpu_stream_refill.argtypes = [PP, PS, PA, C.POINTER(CaCaseStream), _P]
+    L.cagpu_episode_metrics_carry_bytes.argtypes = [PP]
+    L.cagpu_episode_metrics_carry_bytes.restype = C.c_uint64
+    L.cagpu_episode_metrics.argtypes = [PP, C.POINTER(CaTraj), C.c_int32, C.POINTER(CaEpMetrics), _P]
     L.cagpu_device_faults.argtypes = [_P, C.c_int32]
     L.cagpu_device_faults_async.argtypes = [_P, _P]
     L.cagpu_workspace_bytes.argtypes = [PP]
@@ -223,7 +232,7 @@ def lib():
     for n in EXPORTS:
         getattr(L, n)  # AttributeError if a declared symbol is missing
         if n not in ("cagpu_last_error", "cagpu_last_kernel", "cagpu_workspace_bytes", "cagpu_ga3c_packed_bytes",
-                     "cagpu_render_work_bytes"):
+                     "cagpu_render_work_bytes", "cagpu_episode_metrics_carry_bytes"):
             getattr(L, n).restype = C.c_int
     L.cagpu_last_error.restype = C.c_char_p
     L.cagpu_last_kernel.restype = C.c_char_p

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from . import episode_metrics
 from . import episodes
 
 _F64 = ("pos_x", "pos_y", "vel_x", "vel_y", "heading", "goal_x", "goal_y", "radius", "pref_speed",
@@ -179,6 +180,9 @@ class BatchedSim(object):
         # the episode log (log_episodes): None = off; dict(rows [E, C, N, 4] f64, head [E, C, 4] i32, cursor [E] i64, cap)
         self._log = None
         self._cl = nat.CaEpLog()
+        # the episode metrics (measure_episodes): None = off; dict(vals, cnts [E, C, N, 4], head [E, C], cursor [E] i64,
+        # carry [E, bytes] u8, cap, keep_tape, cm=CaEpMetrics, ct=CaTraj of the slots being fed, own_tape)
+        self._met = None
         # the case stream (set_case_stream): None = off; dict(c=CaCaseStream, ref, its tensors, every, since, dist)
         self._cstream = None
 
@@ -634,6 +638,8 @@ class BatchedSim(object):
                 self.keep_final(False)
             if self._log is not None:   # (... and no episode is ever logged)
                 self.log_episodes(on=False)
+            if self._met is not None:   # (... or measured)
+                self.measure_episodes(on=False)
             return
         t = self._dev(table, torch.float64)
         assert t.dim() == 3 and t.shape[1:] == (self.N, 6), t.shape
@@ -745,6 +751,9 @@ class BatchedSim(object):
             self._stream_refill()
         if self._log is not None:   # the reset envs count their episodes from 0 again: undrained records of theirs are discarded
             episodes.clear(self._log["head"], self._log["cursor"], m)
+        if self._met is not None:   # ... and so are their metrics, the running episode's carry included
+            self._met_process()
+            episode_metrics.clear(self._met["head"], self._met["cursor"], self._met["carry"], m)
         if self._traj is not None:   # a host-side reset logs no row but ends the episode of the envs it touches (tape "epoch")
             tr = self._traj
             tr["epoch"] = tr["epoch"] + (1 if m is None else (m != 0).to(torch.int32))
@@ -949,6 +958,8 @@ class BatchedSim(object):
                 self._fault_probe()
         else:
             self._keep = [e]
+        if self._met is not None:
+            self._met_process()
         if self._variants:
             self._apply_sensor_variants()
         return self._obs, self._rewards, self._game_over
@@ -974,6 +985,8 @@ class BatchedSim(object):
                                 C.byref(sx), self._stream_handle()))
         if chunk is not None:
             self._traj_commit(chunk)
+            if self._met is not None:
+                self._met_process()
         self._keep = [e]
         self._apply_sensor_variants()
         return self._obs, self._rewards, self._game_over
@@ -1042,6 +1055,8 @@ class BatchedSim(object):
             self._cs.ext_state, self._ext_state = None, None
         if self._cstream is not None:   # (a ring is launched only when the previous one is used up or sync() has rewound)
             self._stream_refill()
+        if self._met is not None:       # (the last ring's slots were all handed out: measured, and released, before the
+            self._met_process()         #  tape's budget is asked for this one)
         rec = self._traj_on      # (one look per fill: with recording off a fill does what it did before the tape existed)
         if rec:
             fit = self._traj_fit()   # (a full tape raises here, before anything changes)
@@ -1186,6 +1201,8 @@ class BatchedSim(object):
             if t > 0:              # (rewrites slot t - 1 with the values it already holds)
                 nat.check(self._launch(self._p_ref, self._cs_ref, self._co_ref, None, self._ar_ref,
                                         C.byref(nat.CaStepEx(n_steps=t)), self._stream_handle()))
+        if self._met is not None:   # (the t slots handed out; the replay above recorded nothing)
+            self._met_process()
 
     # ---------------------------------------------------------------- the final record (include/cagpu.h CaFinal)
     @property
@@ -1290,8 +1307,120 @@ class BatchedSim(object):
         out, lg["cursor"] = episodes.drain(lg["rows"], lg["head"], lg["cursor"], self._handed_out_reset_count())
         return out
 
+    # ---------------------------------------------------------------- the episode metrics (include/cagpu.h CaEpMetrics)
+    def measure_episodes(self, capacity=16, keep_tape=False, on=True):
+        """Measure every episode on the device: per agent path_length, min_gap (the closest approach to anybody, its
+        partner and time), turn_sum and the steps it moved / spent inside Config.GETTING_CLOSE_RANGE of somebody
+        (DESIGN.md section 3j states the rules, tests/episode_metrics_ref.py restates them in NumPy and the kernel
+        reproduces that file bit for bit).  A reduction kernel of its own (cagpu_episode_metrics) reads the trajectory
+        tape -- recording is switched on if it is off -- after every launch: exactly the slots handed out, once each,
+        whether they came from step(), rollout() or a look-ahead ring (the part of the ring behind the step handed out;
+        a rewind's replay records nothing); no step kernel changes, and state, outputs and statistics are bit-identical to
+        a run without it.  Env e's k-th episode goes to slot k % capacity of its ring -- log_episodes' rule, so the records
+        join the log's by (env, episode) --; episode_metrics() drains what is new.  The episode that is RUNNING takes its
+        slot with its first measured step: `capacity` has to cover the episodes an env can finish between two drains
+        plus one.
+        keep_tape=False: the tape is transient -- measured chunks are released and their bytes returned to the tape's
+        budget, so an arbitrarily long run stays within record_trajectories' max_bytes; trajectories(), render_episode()
+        and render_frames(episode=...) then see only what has not been measured yet (nothing, after a sync).  What the tape
+        held when this was called is never measured and never released.  keep_tape=True: the tape is kept as
+        record_trajectories() keeps it.
+        path_length integrates with CaParams.dt (update_params(dt=...) counts from the next measured slot on): the
+        env API's per-call `dt` of a single step is not seen.  An episode that is under way when this is switched on is
+        measured from here on only -- switch it on in front of a reset for whole episodes.  Needs a fixture table
+        (set_fixture_table), as log_episodes does; detaching the table switches it off.  reset() discards the running
+        episode and the undrained records of the envs it resets.  on=False: pending slots are measured, the records are
+        dropped, and recording stops if this call had started it.  Off by default: a sim that never calls this runs the
+        calls and kernels it ran before."""
+        self.sync()
+        if self._met is not None:
+            self._met_process()
+        if not on:
+            if self._met is not None:
+                own = self._met["own_tape"]
+                self._met = None
+                if own and self._traj_on:
+                    self.stop_recording()
+            return
+        if self._ar is None:
+            raise nat.CagpuError("measure_episodes: no fixture table attached (set_fixture_table): without auto-reset the "
+                                 "episodes of an env are not numbered")
+        cap = int(capacity)
+        if cap < 1:
+            raise nat.CagpuError("measure_episodes: capacity must be >= 1")
+        own = not self._traj_on
+        if own:
+            self.record_trajectories(**({} if self._traj is None else {"max_bytes": self._traj["max_bytes"]}))
+        tr = self._traj
+        for c in tr["chunks"]:      # what the tape holds already stays as it is: not measured, not released
+            c["met"], c["kept"] = c["n"], True
+        tr["block"], tr["open"] = None, None
+        E, N, dev = self.E, self.N, self.device
+        per_env = int(self.lib.cagpu_episode_metrics_carry_bytes(self._p_ref)) // E
+        mt = dict(vals=torch.zeros((E, cap, N, 4), dtype=torch.float64, device=dev),
+                  cnts=torch.zeros((E, cap, N, 4), dtype=torch.int32, device=dev),
+                  head=torch.full((E, cap), -1, dtype=torch.int32, device=dev),
+                  carry=torch.zeros((E, per_env), dtype=torch.uint8, device=dev),
+                  cursor=self._state["reset_count"].to(torch.int64), cap=cap, keep_tape=bool(keep_tape), own_tape=own,
+                  ct=nat.CaTraj())
+        mt["cm"] = nat.CaEpMetrics(vals=mt["vals"].data_ptr(), cnts=mt["cnts"].data_ptr(), head=mt["head"].data_ptr(),
+                                   capacity=cap, carry=mt["carry"].data_ptr(), getting_close_range=self.p.getting_close_range)
+        self._met = mt
+
+    def _met_process(self):
+        """feed cagpu_episode_metrics every tape slot that was handed out and is not measured yet, in step order; with
+        keep_tape=False the chunks measured to their end are released (their bytes go back to the tape's budget, the slot
+        of a step() block is taken again by the next step -- behind the kernel that read it, on the same stream)"""
+        mt, tr = self._met, self._traj
+        if mt is None or tr is None:
+            return
+        la = self._la
+        live = la.get("traj") if (la is not None and la["slots"] is not None and la["t"] < la["len"]) else None
+        per_slot, kept = self.E * self.N * 96, []
+        mt["cm"].getting_close_range = self.p.getting_close_range
+        for c in tr["chunks"]:
+            n = min(c["n"], la["t"]) if c is live else c["n"]
+            m = c.get("met", 0)
+            if n > m:
+                mt["ct"].rows = c["rows"].data_ptr() + (c["start"] + m) * per_slot
+                mt["ct"].episode = c["ep"].data_ptr() + (c["start"] + m) * self.E * 4
+                nat.check(self.lib.cagpu_episode_metrics(self._p_ref, C.byref(mt["ct"]), n - m, C.byref(mt["cm"]),
+                                                         self._stream()))
+                c["met"] = n
+            if mt["keep_tape"] or c is live or c.get("kept") or c.get("met", 0) < c["n"]:
+                kept.append(c)
+                continue
+            tr["bytes"] -= c["n"] * self.traj_step_bytes
+            if c is tr["open"]:
+                tr["open"] = None
+            b = tr["block"]
+            if b is not None and b["rows"] is c["rows"] and b["used"] == c["start"] + c["n"]:
+                b["used"] = c["start"]
+        tr["chunks"] = kept
+
+    def episode_metrics(self):
+        """Drain the episode metrics -> dict of device tensors with the M episodes finished since the last drain, ordered
+        by (env, episode) as episodes() orders the log's: `env`, `episode` [M] int64; `path_length`, `min_gap`, `turn_sum`,
+        `min_gap_t` [M, N] float64; `moved_steps`, `close_steps`, `min_gap_partner` [M, N] int32 -- an agent that never had
+        anybody to be close to has min_gap +inf, min_gap_t NaN, min_gap_partner -1; an absent slot all zeros with those --
+        and `dropped`, a Python int: the episodes that ended since the last drain but whose records were overwritten first.
+        Episodes of steps a look-ahead ring has computed but not handed out stay for a later drain; the call neither
+        rewinds nor drops the ring.  Synchronises with the device (M is read back)."""
+        if self._met is None:
+            raise nat.CagpuError("episode_metrics: the episode metrics are off (measure_episodes)")
+        self._met_process()
+        mt = self._met
+        out, mt["cursor"] = episode_metrics.drain(mt["vals"], mt["cnts"], mt["head"], mt["cursor"],
+                                                  self._handed_out_reset_count())
+        return out
+
     # ---------------------------------------------------------------- the trajectory tape (include/cagpu.h CaTraj)
     TRAJ_BLOCK_BYTES = 8 << 20   # step(): slots are taken from blocks of about this size (at most 64 slots), not a tensor per step
+
+    @property
+    def tape_bytes(self):
+        """bytes of the tape's budget (record_trajectories' max_bytes) in use"""
+        return 0 if self._traj is None else self._traj["bytes"]
 
     @property
     def traj_step_bytes(self):
@@ -1314,13 +1443,18 @@ class BatchedSim(object):
         self._traj_switch(True)
 
     def stop_recording(self):
-        """the steps from here on are not recorded; the tape stays readable (trajectories()) until clear_trajectories()"""
+        """the steps from here on are not recorded (nor measured: measure_episodes); the tape stays readable
+        (trajectories()) until clear_trajectories()"""
         self.sync()
+        if self._met is not None:
+            self._met_process()
         self._traj_switch(False)
 
     def clear_trajectories(self):
         """forget the tape recorded so far (T = 0); recording stays as it is (on / off, budget)"""
         self.sync()
+        if self._met is not None:   # (what was handed out is measured before it goes)
+            self._met_process()
         tr = self._traj
         if tr is not None:
             tr["chunks"], tr["bytes"], tr["block"], tr["open"] = [], 0, None, None
@@ -1395,7 +1529,8 @@ class BatchedSim(object):
           episode  int32 [T, E]: the env's auto-reset count as the step started;
           epoch    int32 [T, E]: the host-side resets (reset() / reset_from_table()) of the env since recording began --
                    a reset logs no row but ends the episode (trajectory.episodes splits where either counter changes).
-        T = the steps handed out (goes through sync()).  Returns copies."""
+        T = the steps handed out (goes through sync()).  Returns copies.  With measure_episodes(keep_tape=False) the tape
+        is transient: only the slots not measured yet are here -- none, once the sync has measured them."""
         self.sync()
         tr = self._traj
         E, N, dev = self.E, self.N, self.device

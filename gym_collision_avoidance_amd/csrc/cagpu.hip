@@ -659,6 +659,7 @@ __host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~static_
 #include "cagpu_scan.inc"
 #include "cagpu_occ.inc"
 #include "cagpu_render.inc"
+#include "cagpu_metrics.inc"
 #include "cagpu_ga3c.inc"
 #include "cagpu_gen.inc"
 
@@ -3121,6 +3122,40 @@ int cagpu_debug_copy8(int64_t n, const double* src, double* dst, void* stream) {
                      static_cast<long>(n), src, dst);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
+}
+
+uint64_t cagpu_episode_metrics_carry_bytes(const CaParams* p) {
+  if (!p || p->num_envs < 1 || p->num_agents < 1 || p->num_agents > 1024) return 0;
+  return static_cast<uint64_t>(p->num_envs) * metrics_carry_env_bytes(p->num_agents);
+}
+
+int cagpu_episode_metrics(const CaParams* p, const CaTraj* traj, int32_t n_steps, const CaEpMetrics* m, void* stream) {
+  if (!p || !traj || !m) return fail(CA_EINVAL, "cagpu_episode_metrics: NULL argument%s");
+  if (p->num_envs < 1 || p->num_agents < 1 || p->num_agents > 1024) return fail(CA_EINVAL, "cagpu_episode_metrics: bad sizes%s");
+  const auto bad = [](const void* q, uintptr_t mask) { return !q || (reinterpret_cast<uintptr_t>(q) & mask); };
+  if (bad(traj->rows, 15) || bad(traj->episode, 3))
+    return fail(CA_EINVAL, "cagpu_episode_metrics: traj->rows NULL or not 16-byte aligned, or traj->episode NULL or not 4-byte aligned%s");
+  if (bad(m->vals, 15) || bad(m->cnts, 15) || bad(m->head, 3) || bad(m->carry, 15))
+    return fail(CA_EINVAL, "cagpu_episode_metrics: vals / cnts / carry NULL or not 16-byte aligned, or head NULL or not 4-byte aligned%s");
+  if (m->capacity < 1) return fail(CA_EINVAL, "cagpu_episode_metrics: capacity < 1%s");
+  if (n_steps < 0) return fail(CA_EINVAL, "cagpu_episode_metrics: n_steps < 0%s");
+  if (n_steps == 0) return CA_OK;
+  MetricsArgs k;
+  k.rows = traj->rows; k.episode = traj->episode;
+  k.vals = m->vals; k.cnts = m->cnts; k.head = m->head; k.carry = static_cast<unsigned char*>(m->carry);
+  k.E = p->num_envs; k.N = p->num_agents; k.T = n_steps; k.C = m->capacity;
+  k.dt = p->dt; k.close_range = m->getting_close_range;
+  const int nt = (p->num_agents + 63) & ~63;
+  const size_t lds = static_cast<size_t>(nt) * 28;
+  if (nt == 64)
+    hipLaunchKernelGGL(metrics_kernel<64>, dim3(static_cast<unsigned>(k.E)), dim3(64), lds, static_cast<hipStream_t>(stream), k);
+  else
+    hipLaunchKernelGGL(metrics_kernel<1024>, dim3(static_cast<unsigned>(k.E)), dim3(nt), lds, static_cast<hipStream_t>(stream), k);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  std::snprintf(g_last_kernel, sizeof(g_last_kernel), "metrics_kernel<%d> grid=%d threads=%d lds=%zu steps=%d", nt == 64 ? 64 : 1024,
+                k.E, nt, lds, n_steps);
   return CA_OK;
 }
 

@@ -144,6 +144,7 @@ class CollisionAvoidanceEnv(Env):
         self._traj_req = None     # record_trajectories(): dict(max_bytes) while recording is asked for
         self._final_req = False   # keep_final_observations()
         self._log_req = None      # log_episodes(): the capacity asked for (None: default) while the log is asked for
+        self._met_req = None      # measure_episodes(): {"capacity", "keep_tape"} while the metrics are asked for
 
     # ------------------------------------------------------------------ configuration (reference setters)
     def set_agents(self, agents):
@@ -566,6 +567,10 @@ class CollisionAvoidanceEnv(Env):
                 self._check_log()
                 if sim._log is None:
                     sim.log_episodes(capacity=self._log_capacity())
+            if self._met_req is not None:    # (likewise)
+                self._check_log("measure_episodes()")
+                if sim._met is None:
+                    sim.measure_episodes(capacity=self._met_capacity(), keep_tape=self._met_req["keep_tape"])
             idx = np.arange(E) if self._streamed(f) else (np.arange(E) + f["env_id_offset"]) % len(f["table"])
             if hasattr(f["table"], "data_ptr"):
                 import torch
@@ -1111,15 +1116,47 @@ class CollisionAvoidanceEnv(Env):
             return cap
         return self.LOG_CAPACITY
 
-    def _check_log(self):
+    def _check_log(self, who="log_episodes()"):
         if self.num_envs <= 1:
-            raise ValueError("log_episodes() is for batched envs (num_envs > 1)")
+            raise ValueError("%s is for batched envs (num_envs > 1)" % who)
         if self._fixture is None and (self.default_agents is not None or self._sim is not None):
-            raise ValueError("log_episodes() needs the on-device auto-reset of set_fixture_suite(..., auto_reset=True): "
-                             "without it no episode ends on the device")
+            raise ValueError("%s needs the on-device auto-reset of set_fixture_suite(..., auto_reset=True): "
+                             "without it no episode ends on the device" % who)
         if self._fixture is not None and not self._fixture["auto_reset"]:
-            raise ValueError("log_episodes() with auto_reset=False: no env is ever reset on the device, read the state "
-                             "when game_over shows")
+            raise ValueError("%s with auto_reset=False: no env is ever reset on the device, read the state "
+                             "when game_over shows" % who)
+
+    def measure_episodes(self, on=True, capacity=None, keep_tape=False):
+        """Batched mode with on-device auto-reset: measure every episode on the device (core.BatchedSim.measure_episodes:
+        per agent path_length, min_gap with its partner and time, turn_sum, moved_steps, close_steps -- a reduction kernel
+        over the trajectory tape, which becomes transient unless keep_tape is set).  With the log on as well
+        (log_episodes) episode_log() gains the metric columns; episode_metrics() drains them on their own.  `capacity`:
+        episodes held per env (default: the log's), one of them the running episode.  May be called before or after
+        reset() and survives reset() (which discards what was not drained).  Off (the default): nothing changes."""
+        if not on:
+            self._met_req = None
+            if self._sim is not None and self._sim._met is not None:
+                self._sim.measure_episodes(on=False)
+            return
+        self._met_req = {"capacity": None if capacity is None else int(capacity), "keep_tape": bool(keep_tape)}
+        self._check_log("measure_episodes()")
+        if self._sim is not None:
+            self._sim.measure_episodes(capacity=self._met_capacity(), keep_tape=bool(keep_tape))
+
+    def _met_capacity(self):
+        cap = self._met_req["capacity"]
+        if cap is not None:
+            return cap
+        return self._log_capacity() if self._log_req is not None else self.LOG_CAPACITY
+
+    def episode_metrics(self):
+        """The metrics of the episodes finished since the last call, ordered by (env, episode) -> dict of numpy arrays:
+        `env`, `episode` [M]; `path_length`, `min_gap`, `turn_sum`, `min_gap_t` [M, N] float64; `moved_steps`,
+        `close_steps`, `min_gap_partner` [M, N] int32; `dropped` (int).  episode_log() drains the same records when both
+        are on: use one of the two.  Does not rewind the look-ahead ring."""
+        if self._sim is None or self._sim._met is None:
+            raise RuntimeError("episode_metrics(): the episode metrics are off (measure_episodes(), then reset())")
+        return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in self._sim.episode_metrics().items()}
 
     def episode_log(self):
         """The episodes finished since the last call (or since log_episodes()), ordered by (env, episode) -> dict of numpy
@@ -1127,12 +1164,31 @@ class CollisionAvoidanceEnv(Env):
         (slots that hold an agent), `steps` [M]; `total_reward`, `time_to_goal`, `extra_time_to_goal` [M, N] (0 in empty
         slots); `total_time_to_goal`, `collision`, `all_at_goal`, `any_stuck`, `outcome` ("collision" / "all_at_goal" /
         "stuck") [M] -- and `dropped`, the number of episodes that ended but were overwritten before this call (int).
-        `env` is this shard's env index (add env_id_offset for the global one).  Does not rewind the look-ahead ring."""
+        `env` is this shard's env index (add env_id_offset for the global one).  Does not rewind the look-ahead ring.
+        With measure_episodes() on, additionally `path_length`, `min_gap`, `turn_sum`, `min_gap_t` [M, N] float64 (NaN where
+        the record has no metrics) and `moved_steps`, `close_steps`, `min_gap_partner` [M, N] int32 (-1 there), filled for
+        every record whose (env, episode) is in the metrics' drain as well, `has_metrics` [M] bool saying which, and
+        `metrics_dropped` (int)."""
         if self._sim is None or self._sim._log is None:
             raise RuntimeError("episode_log(): the episode log is off (log_episodes(), then reset())")
         from gym_collision_avoidance_amd import episodes as eplog
         ep = self._sim.episodes()
-        return eplog.suite_columns({k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in ep.items()})
+        out = eplog.suite_columns({k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in ep.items()})
+        if self._sim._met is not None:
+            from gym_collision_avoidance_amd import episode_metrics as epmet
+            met = self.episode_metrics()
+            li, cols = epmet.join(out, met)
+            M, N = len(out["env"]), self._sim.N
+            out["has_metrics"] = np.zeros(M, bool)
+            out["has_metrics"][li] = True
+            for n in epmet.FLOAT_COLUMNS:
+                out[n] = np.full((M, N), np.nan)
+                out[n][li] = cols[n]
+            for n in epmet.INT_COLUMNS:
+                out[n] = np.full((M, N), -1, np.int32)
+                out[n][li] = cols[n]
+            out["metrics_dropped"] = int(met["dropped"])
+        return out
 
     def _resize_ring(self):
         """the default ring length follows the bytes of a slot (see _upload): recomputed when the final record is toggled"""

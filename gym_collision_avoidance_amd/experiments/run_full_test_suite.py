@@ -74,13 +74,16 @@ def run_suite(policy="RVO", num_agents=4, test_cases=None, device="cuda:0", max_
     return pd.DataFrame(rows)
 
 
-def run_suite_logged(policy="RVO", num_agents=4, test_cases=None, num_envs=None, device="cuda:0", chunk=256, max_steps=200000):
+def run_suite_logged(policy="RVO", num_agents=4, test_cases=None, num_envs=None, device="cuda:0", chunk=256, max_steps=200000,
+                     metrics=False):
     """run_suite() through the on-device episode log (CollisionAvoidanceEnv.log_episodes): `num_envs` envs (default
     min(number of cases, 64)) walk the table of `test_cases` with the on-device auto-reset -- env e runs cases e,
     e + num_envs, ... --, env.rollout() advances the batch `chunk` steps per call (one fused launch where every policy is
     answered inside the step kernel) and the log is drained after every chunk until every case has its first record.
     No env per case, no per-step latching on the host.  -> the same DataFrame as run_suite, one row per case, in case order
-    (bit for bit where a case is the first episode of its env; later episodes start from the device's own arctan2)."""
+    (bit for bit where a case is the first episode of its env; later episodes start from the device's own arctan2).
+    metrics=True: the episode metrics are measured as well (CollisionAvoidanceEnv.measure_episodes, a transient tape) and
+    every row gains `path_length`, `min_gap`, `turn_sum` (float arrays per agent) and `close_steps` (int array)."""
     import pandas as pd
     spec = policies[policy]
     cases = list(range(len(tc.fixture_table(num_agents)))) if test_cases is None else list(test_cases)
@@ -101,6 +104,8 @@ def run_suite_logged(policy="RVO", num_agents=4, test_cases=None, num_envs=None,
                           agents_sensors=tuple(spec.get("sensors", ["other_agents_states"])), agent_setup=setup)
     # an env finishes at most one episode per step: a capacity of `chunk` can never overflow between two drains
     env.log_episodes(capacity=int(chunk))
+    if metrics:    # (one slot more than the log's: the running episode holds one)
+        env.measure_episodes(capacity=int(chunk) + 1)
     env.reset()
     if Config.EVALUATE_MODE:
         # run_suite's initial state, bit for bit: the reference gives every agent the heading numpy's arctan2 computes
@@ -116,9 +121,11 @@ def run_suite_logged(policy="RVO", num_agents=4, test_cases=None, num_envs=None,
         steps += int(chunk)
         log = env.episode_log()
         assert log["dropped"] == 0, log["dropped"]
+        if metrics:
+            assert log["metrics_dropped"] == 0 and bool(log["has_metrics"].all()), log["metrics_dropped"]
         for i, c in enumerate(log["test_case"]):    # (a case several envs ran: the record with the lowest episode index)
             if int(c) not in first or int(log["episode"][i]) < int(first[int(c)]["episode"]):
-                first[int(c)] = {k: v[i] for k, v in log.items() if k != "dropped"}
+                first[int(c)] = {k: v[i] for k, v in log.items() if k not in ("dropped", "metrics_dropped")}
     rows = []
     for j, c in enumerate(cases):
         r = first[j]     # (cases the batch never finished within max_steps raise here)
@@ -128,6 +135,8 @@ def run_suite_logged(policy="RVO", num_agents=4, test_cases=None, num_envs=None,
                      "time_to_goal": ttg, "total_time_to_goal": float(ttg.sum()),
                      "extra_time_to_goal": np.array(r["extra_time_to_goal"]), "collision": bool(r["collision"]),
                      "all_at_goal": bool(r["all_at_goal"]), "any_stuck": bool(r["any_stuck"]), "outcome": str(r["outcome"])})
+        if metrics:
+            rows[-1].update({n: np.array(r[n]) for n in ("path_length", "min_gap", "turn_sum", "close_steps")})
     return pd.DataFrame(rows)
 
 

@@ -307,6 +307,33 @@ typedef struct CaEpLog {
   int32_t capacity, reserved0;   /* C >= 1 */
 } CaEpLog;
 
+/* Episode metrics (cagpu_episode_metrics; additive to v12): per-episode path and closest-approach numbers of every agent,
+ * reduced from trajectory-tape slots (CaTraj) by a kernel of their own -- no step kernel knows about them.  The rules
+ * (tests/episode_metrics_ref.py is their float64 NumPy statement, which the kernel reproduces bit
+ * for bit): per env the slots are walked in step order, k = episode[t, e]; an agent has MOVED in a slot where column 11 is
+ * >= 0 (columns 0 - 10 of any other row are never read).  Within a slot every moved row first gives its position
+ * (columns 1, 2) and radius (5) and marks its agent `seen`; then, per moved agent a:
+ *   moved_steps += 1;  path_length += sqrt(vx * vx + vy * vy) * CaParams.dt  (columns 7, 8);
+ *   turn_sum += fabs(remainder(heading - last heading, 2 pi)) from the agent's second row of the episode on (column 10);
+ *   over the seen agents j != a: g = (sqrt(dx * dx + dy * dy) - radius[a]) - radius[j], its minimum g_min (ties: lowest j);
+ *   if there is such a j: close_steps += (g_min <= getting_close_range), and where g_min < min_gap strictly:
+ *   min_gap = g_min, min_gap_partner = j, min_gap_t = column 0 of a's row.
+ * An agent that is done stays seen, where it stopped, until the episode ends; an agent that never moved in the episode is
+ * never seen.  Where episode[t, e] differs from the carried episode id the finished episode's record is written and the
+ * env's carry cleared; at the end of every call each env also writes the record of its RUNNING episode (a later call
+ * overwrites it).  Episode k of env e goes to slot k % capacity and is valid where head[e, k % capacity] == k -- CaEpLog's
+ * rule; a running episode therefore takes the slot of the episode `capacity` before it with its first processed step.
+ * Defaults of an agent without a partner: min_gap +inf, min_gap_t NaN, min_gap_partner -1. */
+typedef struct CaEpMetrics {
+  double  *vals;   /* device [E, C, N, 4], 16-byte aligned: path_length, min_gap, turn_sum, min_gap_t */
+  int32_t *cnts;   /* device [E, C, N, 4], 16-byte aligned: moved_steps, close_steps, min_gap_partner, 0 */
+  int32_t *head;   /* device [E, C], 4-byte aligned: the stamp k; the caller fills it with -1 */
+  int32_t capacity, reserved0;   /* C >= 1 */
+  void    *carry;  /* device, cagpu_episode_metrics_carry_bytes(p) bytes, 16-byte aligned, ZEROED by the caller: env e owns
+                      bytes [e, e + 1) x (carry bytes / E); zeroing an env's share forgets its running episode */
+  double getting_close_range;   /* Config.GETTING_CLOSE_RANGE (CaParams.getting_close_range) */
+} CaEpMetrics;
+
 /* Frames of cagpu_render / cagpu_render_maps (additive to v12): F pictures of height x width pixels, each of ONE env, drawn from the
  * current state, the env's static map and a block of trajectory-tape rows by the drawing rules of DESIGN.md section 13.
  * The window: pixel (row r, column c) has its centre at x = xmin + (16 c + 8) / s16, y = ymax - (16 r + 8) / s16,
@@ -821,6 +848,15 @@ int cagpu_debug_libm(int32_t op, int32_t n, const double *a, const double *b, do
  * bytes read, 8 n written), which is what the rocprofv3 FETCH_SIZE / WRITE_SIZE counters of the step kernels are calibrated
  * against (profiles/r05_traffic.json: the counters under-report this pattern on gfx950). */
 int cagpu_debug_copy8(int64_t n, const double *src, double *dst, void *stream);
+
+/* Episode metrics (CaEpMetrics, additive to v12): process slots 0 .. n_steps - 1 of `traj` -- n_steps CONSECUTIVE steps of
+ * the run, following the slots of the previous call on the same carry --; traj->rows and traj->episode are both needed.
+ * Only num_envs, num_agents (1 .. 1024) and dt of `p` are read.  CA_EINVAL: a NULL pointer, traj->rows / vals / cnts / carry
+ * not 16-byte aligned, traj->episode / head not 4-byte aligned, capacity < 1, n_steps < 0.  n_steps == 0 does nothing.
+ * Asynchronous on `stream`; cagpu_last_kernel() names the kernel (metrics_kernel<64>: one wavefront per env up to 64
+ * agents; metrics_kernel<1024>: one workgroup per env). */
+uint64_t cagpu_episode_metrics_carry_bytes(const CaParams *p);   /* 0 for bad sizes; host-only call */
+int cagpu_episode_metrics(const CaParams *p, const CaTraj *traj, int32_t n_steps, const CaEpMetrics *m, void *stream);
 
 #ifdef __cplusplus
 }
