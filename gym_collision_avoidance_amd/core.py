@@ -139,6 +139,9 @@ class BatchedSim(object):
         self._step_ex = self.lib.cagpu_step_ex
         # ... except while a policy draw is on (set_policy_draw): _launch is then cagpu_step_draw with the draw bound in
         self._launch = self._step_ex
+        # ... and a fused launch (rollout, ring fill, a rewind's replay) of a batch with a map: cagpu_step_ex_maps, the one
+        # entry point that admits CaStepEx.map / .set with n_steps > 1 or ring (_launch_n)
+        self._step_ex_maps = self.lib.cagpu_step_ex_maps
         self._draw = None         # the policy draw: dict(c=CaPolicyDraw, cdf, bits, has_ga3c) / None
         self._sx = nat.CaStepEx(n_steps=1)
         self._p_ref, self._cs_ref, self._co_ref, self._sx_ref = C.byref(self.p), C.byref(self._cs), C.byref(self._co), C.byref(self._sx)
@@ -151,7 +154,7 @@ class BatchedSim(object):
         self._map = None
         self._maps = None         # a map set (set_map with a stack of maps): CaMapSet; env_map is its device index tensor
         self._map_rng = None      # the generator of the map-set key an explicit reset() draws (set_map's map_seed)
-        self.env_map = None
+        self._env_map = None
         self._scan = None
         self.scan = None
         self.occ = None           # OccupancyGridSensor windows (set_occupancy_grid): bool [E, N, H, W] / None
@@ -203,6 +206,9 @@ class BatchedSim(object):
             setattr(self, name, value)
         return property(get, put)
     obs, rewards, done, game_over = _synced("_obs"), _synced("_rewards"), _synced("_done"), _synced("_game_over")
+    # the map of every env of a map set (device int32 [E]; None without a set), at the step last handed out: an auto-reset
+    # of a look-ahead ring that has run ahead has already drawn the maps of episodes not handed out yet
+    env_map = _synced("_env_map")
     # the final record of the step last handed out (keep_final; None while it is off): float32 [E, N, W] / int32 [E, N]
     # (uint32 bit patterns, nat.decode_flags), rows valid where `game_over` is set
     final_obs, final_flags = _synced("_fin_obs"), _synced("_fin_flags")
@@ -716,6 +722,12 @@ class BatchedSim(object):
         # (any slot may become a GA3C-CADRL agent at an auto-reset: the network then runs before every step)
         self._has_ga3c = self._plugins_ga3c or has_ga3c
 
+    def _launch_n(self, p, s, o, ext, ar, sx, stream):
+        """a fused launch: _launch, or -- where the CaStepEx names a map or a set -- cagpu_step_ex_maps with the draw"""
+        if self._map is None:
+            return self._launch(p, s, o, ext, ar, sx, stream)
+        return self._step_ex_maps(p, s, o, ext, ar, sx, None if self._draw is None else self._draw["ref"], stream)
+
     def _policy_draw_now(self, mask=None):
         """cagpu_policy_draw: the lottery of the episode every (masked) env is in, on the state and column 0 of `obs`"""
         nat.check(self.lib.cagpu_policy_draw(self._p_ref, self._cs_ref, self._co_ref, self._ar_ref, self._draw["ref"],
@@ -761,6 +773,9 @@ class BatchedSim(object):
         if self._maps is not None and self._map_rng is not None:
             # a fresh key per explicit reset: the auto-reset draws of the new episodes are not those of the last ones
             self._maps.map_seed = int(self._map_rng.integers(1, 1 << 64, dtype=np.uint64))
+            self._map_note_key()
+        if self._maps is not None:
+            self._map_note_assign(m, reset=True)
         self._apply_sensor_variants()
         return self._obs
 
@@ -779,13 +794,14 @@ class BatchedSim(object):
 
         A MAP SET (include/cagpu.h CaMapSet): `static_map` a bool stack [M, rows, cols] -- every env has its own map,
         the device int32 tensor `env_map` [E] (default: env e on map e % M; an explicit one must hold indices in
-        [0, M)), and step() / laserscan() hand the kernels the CaMapSet (CaStepEx.set / cagpu_laserscan_maps).  map_seed != 0:
+        [0, M)), and step(), rollout(), the look-ahead ring and laserscan() hand the kernels the CaMapSet (CaStepEx.set /
+        cagpu_laserscan_maps; a fused launch through cagpu_step_ex_maps).  map_seed != 0:
         every auto-reset of an env draws its next map on the device (the reference draws a map per episode,
         collision_avoidance_env.py:274-275, :384-385) with a key that every explicit reset() draws anew from a generator
         seeded by map_seed (`map_seed` property: the key in force); 0: every env keeps its map."""
         self.sync()
         bits = None
-        self._maps, self._map_rng, self.env_map = None, None, None
+        self._maps, self._map_rng, self._env_map = None, None, None
         self._sx.map, self._sx.set = None, None   # (re-pointed below, once the new structs exist)
         self.occ, self.occ_bits, self._occ = None, None, None   # (sized by the map's cell: set_occupancy_grid() again)
         M = 0
@@ -804,12 +820,16 @@ class BatchedSim(object):
         self._map = nat.CaMap(static_bits=None if bits is None else bits.data_ptr(), rows=rows, cols=cols, cell=cell,
                               origin_r=(rows * cell / 2.) / cell, origin_c=(cols * cell / 2.) / cell)
         if M:
-            self.env_map = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
-            self._maps = nat.CaMapSet(map=self._map, env_map=self.env_map.data_ptr(), num_maps=M, map_seed=0)
+            self._env_map = torch.zeros((self.E,), dtype=torch.int32, device=self.device)
+            self._maps = nat.CaMapSet(map=self._map, env_map=self._env_map.data_ptr(), num_maps=M, map_seed=0)
             self.set_env_map(np.arange(self.E) % M if env_map is None else env_map)
             if int(map_seed):
                 self._map_rng = np.random.Generator(np.random.PCG64(int(map_seed) & 0xFFFFFFFFFFFFFFFF))
                 self._maps.map_seed = int(map_seed) & 0xFFFFFFFFFFFFFFFF
+            # which map an episode ran on (episodes()' `map` column; episodes.map_column has the rule): the index an env was
+            # GIVEN (reset / set_env_map) with the episode it was in, and the first episode whose draw used the key in force
+            self._map_key_from = torch.zeros((self.E,), dtype=torch.int64, device=self.device)
+            self._map_note_assign()
         # a single step takes the set, or else the one map (set_map_seed / set_env_map rewrite the CaMapSet / its tensor in place)
         if M:
             self._sx.set = C.addressof(self._maps)
@@ -837,7 +857,26 @@ class BatchedSim(object):
         """replace the key of the map set's auto-reset draws (0: off); the next explicit reset() draws a new one only
         where set_map was given a map_seed"""
         assert self._maps is not None, "set_map() with a stack of maps first"
+        self.sync()   # (a ring that ran ahead drew with the old key)
         self._maps.map_seed = int(key) & 0xFFFFFFFFFFFFFFFF
+        self._map_note_key()
+
+    def _map_note_key(self):
+        """the key changed: the draws of reset counts above the current ones use it"""
+        self._map_key_from = self._state["reset_count"].to(torch.int64) + 1
+
+    def _map_note_assign(self, mask=None, reset=False):
+        """the envs of `mask` (None: all) were given their map by the host, in the episode they are in now; reset: by an
+        explicit reset, which zeroes their reset counts -- every draw of theirs from now on uses the key in force"""
+        rc = self._state["reset_count"].to(torch.int64)
+        m = torch.ones_like(rc, dtype=torch.bool) if mask is None else mask != 0
+        if mask is None:
+            self._map_ep0, self._map_val0 = rc, self._env_map.clone()
+        else:
+            self._map_ep0 = torch.where(m, rc, self._map_ep0)
+            self._map_val0 = torch.where(m, self._env_map, self._map_val0)
+        if reset:
+            self._map_key_from = torch.where(m, torch.zeros_like(rc), self._map_key_from)
 
     def set_env_map(self, env_map):
         """the map of every env of the map set: ints broadcastable to [E], each in [0, M) (checked here: the device
@@ -850,7 +889,8 @@ class BatchedSim(object):
         M = int(self._maps.num_maps)
         if idx.size and (idx.min() < 0 or idx.max() >= M):
             raise ValueError("env_map holds indices outside [0, %d): %s" % (M, sorted(set(idx[(idx < 0) | (idx >= M)].tolist()))[:8]))
-        self.env_map.copy_(torch.from_numpy(idx.astype(np.int32)))   # (in place: the CaMapSet points at this tensor)
+        self._env_map.copy_(torch.from_numpy(idx.astype(np.int32)))   # (in place: the CaMapSet points at this tensor)
+        self._map_note_assign()
 
     def laserscan(self):
         """'laserscan' observation [E,N,num_to_store,num_beams] of the current state (call after reset / step)."""
@@ -977,11 +1017,12 @@ class BatchedSim(object):
             self._new_outputs()
         if self._cstream is not None:
             self._stream_refill()
-        # the n steps' CaStepEx: no map (as ever), the tape's own chunk, the single-step final block -- it ends up holding every
+        # the n steps' CaStepEx: the map or set of a single step, the tape's own chunk, the single-step final block -- it ends up holding every
         # env's most recent terminal record of the launch -- and the log, every ending in its own slot
         chunk, ct = self._traj_chunk(int(n_steps)) if self._traj_on else (None, None)
-        sx = nat.CaStepEx(n_steps=int(n_steps), traj=None if ct is None else C.addressof(ct), fin=self._sx.fin, log=self._sx.log)
-        nat.check(self._launch(self._p_ref, self._cs_ref, self._co_ref, None if e is None else e.data_ptr(), self._ar_ref,
+        sx = nat.CaStepEx(n_steps=int(n_steps), map=self._sx.map, set=self._sx.set, traj=None if ct is None else C.addressof(ct),
+                          fin=self._sx.fin, log=self._sx.log)
+        nat.check(self._launch_n(self._p_ref, self._cs_ref, self._co_ref, None if e is None else e.data_ptr(), self._ar_ref,
                                 C.byref(sx), self._stream_handle()))
         if chunk is not None:
             self._traj_commit(chunk)
@@ -1014,8 +1055,10 @@ class BatchedSim(object):
     def lookahead_ok(self):
         """can step_lookahead() run this batch?  Every policy has to be answered inside the step kernel and nothing may
         happen BETWEEN two steps on the host or in another kernel: no GA3C-CADRL network, no per-step stochastic RVO
-        draws, no per-agent sensor variants (extra cagpu_observe launches), no static map (wall test + laser scan)."""
-        return not (self._has_ga3c or self._rvo is not None or self._variants or self._map is not None)
+        draws, no per-agent sensor variants (extra cagpu_observe launches).  A static map or a map set is carried by the
+        ring's launches (walls and map draws are those of single steps); laserscan() / occupancy_grid() go through sync()
+        and describe the step last handed out."""
+        return not (self._has_ga3c or self._rvo is not None or self._variants)
 
     def enable_lookahead(self, k, fresh=True, adaptive=False, start=None):
         """Serve step(None) from a ring of `k` steps computed ahead of time in ONE launch (CaStepEx.ring): with every
@@ -1024,7 +1067,8 @@ class BatchedSim(object):
         n-step kernel never waits for the slowest workgroup of a step (7.7 instead of 14.9 us per step at 4096 x 10).
         Results are those of k single launches, bit for bit.  Whatever needs the state of the step last handed out --
         reading `state`, a reset, an external action, a parameter change, the episode statistics -- goes through sync(),
-        which rewinds (restore the snapshot taken before the launch, re-run the steps already handed out).
+        which rewinds (restore the snapshot taken before the launch, re-run the steps already handed out).  `env_map` of a
+        map set is read through sync() as well: a ring that has run ahead has drawn the maps of episodes not handed out yet.
         fresh: every refill writes into a NEWLY allocated ring (what step_lookahead returned stays valid and belongs to
         the caller); False: one persistent ring, a slot is overwritten k steps later.  k = 0: off.
         adaptive: k is the LONGEST ring.  A rewind throws the rest of a ring away, so a caller who looks at the state (or
@@ -1050,7 +1094,7 @@ class BatchedSim(object):
         la = self._la
         if not self.lookahead_ok():
             raise nat.CagpuError("step_lookahead: this batch needs work between two steps (GA3C-CADRL network, stochastic RVO "
-                                 "draws, sensor variants or a static map) -- use step()")
+                                 "draws or sensor variants) -- use step()")
         if self._cs.ext_state:   # (CaState.ext_state belongs to the ONE step() call that was given it: see rollout())
             self._cs.ext_state, self._ext_state = None, None
         if self._cstream is not None:   # (a ring is launched only when the previous one is used up or sync() has rewound)
@@ -1077,6 +1121,8 @@ class BatchedSim(object):
         la["ring"] = prep["ring"]
         if not prep["in_kernel"]:
             la["snap"].copy_(self._slab)
+        if self._maps is not None:   # env_map is not in the slab: the rewind point of a set keeps its own copy (E int32)
+            la["map_snap"] = self._env_map.clone()
         la["fin_ring"] = prep["fin_ring"]
         # the launch's CaStepEx was prepared with the ring (final blocks, the episode log -- its records land in the envs' own
         # rings, not in the output ring); the ring's own chunk of the tape is taken now: slot t of the launch records step t
@@ -1084,7 +1130,7 @@ class BatchedSim(object):
         if rec:
             chunk, ct = self._traj_chunk(k, prep["traj"])
             prep["sx"].traj = C.addressof(ct)
-        rc = self._launch(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], prep["sx_ref"], self._stream_handle())
+        rc = self._launch_n(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], prep["sx_ref"], self._stream_handle())
         if rc != 0:
             nat.check(rc)
         if chunk is not None:
@@ -1102,7 +1148,8 @@ class BatchedSim(object):
         """what decides which kernel a ring call of k steps runs (and with it whether the kernel takes the rewind snapshot)"""
         ar = self._ar
         return (k, self.p.sort_mode, ar is not None and bool(ar.reset_obs), bool(self._cs.next_action),
-                0 if ar is None else int(ar.heading_seed), 0 if ar is None else C.addressof(ar))
+                0 if ar is None else int(ar.heading_seed), 0 if ar is None else C.addressof(ar),
+                int(self._sx.map or 0), int(self._sx.set or 0))
 
     def _la_prepare(self, k):
         la, E, N, dev = self._la, self.E, self.N, self.device
@@ -1136,7 +1183,7 @@ class BatchedSim(object):
         # (the kernels write 0 / 1 bytes: reinterpreted as bool without a conversion kernel)
         slots = list(zip(obs.unbind(0), rew.unbind(0), done.view(torch.bool).unbind(0), over.view(torch.bool).unbind(0)))
         sx = nat.CaStepEx(n_steps=k, ring=1, snapshot_delta=(la["snap"].data_ptr() - self._slab.data_ptr()) if in_kernel else 0,
-                          fin=None if cf is None else C.addressof(cf), log=self._sx.log)
+                          map=self._sx.map, set=self._sx.set, fin=None if cf is None else C.addressof(cf), log=self._sx.log)
         return dict(k=k, key=key, ring=ring, co=co, co_ref=C.byref(co), ar_ref=ar_ref, in_kernel=in_kernel, slots=slots,
                     fin_ring=fin_ring, cf=cf, sx=sx, sx_ref=C.byref(sx),   # (cf: kept alive for sx.fin)
                     traj=self._traj_alloc(k) if self._traj_on else None)   # (always its own tensors, fresh ring or not)
@@ -1198,9 +1245,12 @@ class BatchedSim(object):
                 self._cf.obs, self._cf.flags = self._fin_obs.data_ptr(), self._fin_flags.data_ptr()
         if t < k:
             self._slab.copy_(la["snap"])
+            if self._maps is not None:   # (in place: the CaMapSet points at this tensor)
+                self._env_map.copy_(la["map_snap"])
             if t > 0:              # (rewrites slot t - 1 with the values it already holds)
-                nat.check(self._launch(self._p_ref, self._cs_ref, self._co_ref, None, self._ar_ref,
-                                        C.byref(nat.CaStepEx(n_steps=t)), self._stream_handle()))
+                nat.check(self._launch_n(self._p_ref, self._cs_ref, self._co_ref, None, self._ar_ref,
+                                          C.byref(nat.CaStepEx(n_steps=t, map=self._sx.map, set=self._sx.set)),
+                                          self._stream_handle()))
         if self._met is not None:   # (the t slots handed out; the replay above recorded nothing)
             self._met_process()
 
@@ -1297,7 +1347,9 @@ class BatchedSim(object):
         """Drain the episode log -> dict of device tensors with the M episodes finished since the last drain, ordered by
         (env, episode): `env`, `episode` (the env's k-th episode since its last reset()), `case` (row of the fixture table it
         ran on), `steps`, `outcome` (0 collision / 1 all at goal / 2 stuck) [M] int64; `total_reward`, `time_to_goal`,
-        `extra_time_to_goal` [M, N] float64; `flags` [M, N] int32 (nat.decode_flags) -- and `dropped`, a Python int: the
+        `extra_time_to_goal` [M, N] float64; `flags` [M, N] int32 (nat.decode_flags); with a map set attached `map` [M] int64, the
+        env_map value the env held while the episode ran (-1 where it cannot be known any more: the key was replaced after
+        the episode's map was drawn) -- and `dropped`, a Python int: the
         episodes that ended since the last drain but whose records were overwritten first (capacity too small).  Episodes
         of steps a look-ahead ring has computed but not handed out yet stay in the log for a later drain; the call neither
         rewinds nor drops the ring.  Synchronises with the device (M is read back)."""
@@ -1305,7 +1357,20 @@ class BatchedSim(object):
             raise nat.CagpuError("episodes: the episode log is off (log_episodes)")
         lg = self._log
         out, lg["cursor"] = episodes.drain(lg["rows"], lg["head"], lg["cursor"], self._handed_out_reset_count())
+        if self._maps is not None:
+            out["map"] = self._episode_maps(out["env"], out["episode"])
         return out
+
+    def _episode_maps(self, env, k):
+        """int64 [M]: the env_map value env[i] held while its episode k[i] ran (episodes.map_column; -1: not known)"""
+        key, n = self.map_seed, int(env.shape[0])
+        drawn = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        if key and n:   # cagpu_map_draw: the kernels' own map_draw for (global env id, reset count) pairs
+            ge = (env + int(self._ar.env_id_offset if self._ar is not None else 0)).contiguous()
+            cnt = k.to(torch.int32).contiguous()
+            nat.check(self.lib.cagpu_map_draw(key, self.num_maps, ge.data_ptr(), cnt.data_ptr(), n, drawn.data_ptr(),
+                                              self._stream()))
+        return episodes.map_column(k, self._map_ep0[env], self._map_val0[env], self._map_key_from[env], bool(key), drawn)
 
     # ---------------------------------------------------------------- the episode metrics (include/cagpu.h CaEpMetrics)
     def measure_episodes(self, capacity=16, keep_tape=False, on=True):

@@ -673,6 +673,13 @@ __device__ __forceinline__ int32_t map_draw(const unsigned long long seed, const
   return m < num_maps - 1 ? m : num_maps - 1;
 }
 
+// cagpu_map_draw: map_draw for given (global env id, reset count) pairs
+__global__ __launch_bounds__(256) void map_draw_kernel(const unsigned long long seed, const int num_maps, const int64_t* env_ids,
+                                                        const int32_t* counts, const long n, int32_t* out) {
+  const long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+  if (i < n) out[i] = map_draw(seed, env_ids[i], counts[i], num_maps);
+}
+
 // ---- policy draw (CaPolicyDraw in cagpu.h has the rule).  Its uniform for counter word `slot` of env ge's episode k:
 __device__ __forceinline__ double draw_uniform(const unsigned long long seed, const long ge, const int k, const unsigned slot) {
   const unsigned long long g = static_cast<unsigned long long>(ge);
@@ -801,7 +808,10 @@ __device__ __forceinline__ void reset_lane(Lane& r, const double* c, const bool 
 
 #include "cagpu_rules.inc"
 
-template <int NT, bool STAGE, int NC, bool MULTI, bool RO, int TE = 0>
+// MSET: the n-step form (MULTI) also runs the map-set code of the single-step form -- the per-env grid of A3, the map draw
+// of an auto-reset.  A template flag that only a set launch with n_steps > 1 selects (launch_main4): every other
+// instantiation is the code it was before the flag existed.
+template <int NT, bool STAGE, int NC, bool MULTI, bool RO, int TE = 0, bool MSET = false>
 // n-step: <= 128 VGPRs (four 4-wave workgroups per CU) -- except N = 20, whose single-step form already needs 172 (two
 // workgroups per CU either way): held to 128 its n-step form spilled ~200 VGPRs to scratch around the step loop
 __global__ __launch_bounds__(NT, MULTI ? (NC == 20 ? 2 : 4) : 1) void ca_kernel(const KArgs k) {
@@ -1497,10 +1507,11 @@ LP1_UNROLL
       // ---- A3 (wave 0, while the other waves finish the pair items of P4): rewards + collision flag (env.py:394-456),
       // observation scalars
       if (wave0) PRIO(3, 0, 3, 3, 3, 3, 3, 3);
-      // a map set (single-step kernel only; workgroup-uniform test): the env's grid, its index read by the env's agent 0
-      // lane and handed to the others -- the wall tests of this step see the map the env had when the step began
+      // a map set (the single-step kernel and the n-step form's MSET instantiations; workgroup-uniform test): the env's
+      // grid, its index read by the env's agent 0 lane and handed to the others -- the wall tests of this step see the map
+      // the env had when the step began (in an n-step launch: what the same lane stored at the last step's auto-reset)
       const uint32_t* wall_bits = nullptr;
-      const bool wall_set = !MULTI && k.env_map != nullptr && k.mode == MODE_STEP && pass == 0;
+      const bool wall_set = (!MULTI || MSET) && k.env_map != nullptr && k.mode == MODE_STEP && pass == 0;
       if (wall_set && wave0) {
         int m = (active && a == 0) ? k.env_map[e] : 0;
         m = __shfl(m, ebase);
@@ -1601,7 +1612,7 @@ LP1_UNROLL
               if (RO) sh_flag[lane] = r.flags;  // (the copy of the reset observation takes is_learning from here)
             }
             // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by its agent 0 lane
-            if (!MULTI && k.map_seed && a == 0) k.env_map[e] = map_draw(k.map_seed, k.env_id_offset + e, reset_cnt, k.num_maps);
+            if ((!MULTI || MSET) && k.map_seed && a == 0) k.env_map[e] = map_draw(k.map_seed, k.env_id_offset + e, reset_cnt, k.num_maps);
             ep_step = 0;
             statics_dirty = true;
             if (RO) {
@@ -1880,7 +1891,15 @@ void ring_advance(KArgs& k) {
   if (k.fin_flags) k.fin_flags += k.ring_agent;
 }
 
-template <int NT, bool STAGE, int NC, bool MULTI, bool RO, int TE = 0>
+// what a map or map-set launch adds to cagpu_last_kernel(): " set" where the n-step kernels' MSET instantiations run (a set
+// with n_steps > 1 in one launch), " map" for every other launch with a map or a set -- a single step of a set of one map
+// names the kernel its single map does (a map-less launch: the string it always was)
+void map_suffix(const KArgs& k, const bool mset = false) {
+  const char* sfx = mset ? " set" : ((k.env_map || k.map.static_bits) ? " map" : "");
+  std::strncat(g_last_kernel, sfx, sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
+}
+
+template <int NT, bool STAGE, int NC, bool MULTI, bool RO, int TE = 0, bool MSET = false>
 int launch_main5(const KArgs& k, size_t total, hipStream_t st) {
   // per instantiation and device: raise the dynamic-LDS limit once, not on every launch
   static std::atomic<size_t> lds_limit[64];
@@ -1890,7 +1909,7 @@ int launch_main5(const KArgs& k, size_t total, hipStream_t st) {
   size_t have = lim.load(std::memory_order_relaxed);
   if (have == 0) have = 48 * 1024;
   if (total > have) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ca_kernel<NT, STAGE, NC, MULTI, RO, TE>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ca_kernel<NT, STAGE, NC, MULTI, RO, TE, MSET>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(total));
     if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: hipFuncSetAttribute: %s", hipGetErrorString(e));
     lim.store(total, std::memory_order_relaxed);
@@ -1900,7 +1919,8 @@ int launch_main5(const KArgs& k, size_t total, hipStream_t st) {
   std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_kernel<%d, %s, %d, %s, %s, %d> grid=%u lds=%zu tile_envs=%d",
                 NT, STAGE ? "true" : "false", NC, MULTI ? "true" : "false", RO ? "true" : "false", TE, grid, total,
                 tile_envs);
-  hipLaunchKernelGGL((ca_kernel<NT, STAGE, NC, MULTI, RO, TE>), dim3(grid), dim3(NT), total, st, k);
+  map_suffix(k, MSET);
+  hipLaunchKernelGGL((ca_kernel<NT, STAGE, NC, MULTI, RO, TE, MSET>), dim3(grid), dim3(NT), total, st, k);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
   return CA_OK;
@@ -1908,6 +1928,12 @@ int launch_main5(const KArgs& k, size_t total, hipStream_t st) {
 
 template <int NT, bool STAGE, int NC, bool MULTI, int TE = 0>
 int launch_main4(const KArgs& k, size_t total, hipStream_t st) {
+  if constexpr (MULTI) {  // a map set in an n-step launch: the MSET instantiations (the only launches that select them)
+    if (k.env_map) {
+      if (k.table && k.reset_obs) return launch_main5<NT, STAGE, NC, true, true, TE, true>(k, total, st);
+      return launch_main5<NT, STAGE, NC, true, false, TE, true>(k, total, st);
+    }
+  }
   if (k.mode == MODE_STEP && k.table && k.reset_obs) return launch_main5<NT, STAGE, NC, MULTI, true, TE>(k, total, st);
   return launch_main5<NT, STAGE, NC, MULTI, false, TE>(k, total, st);
 }
@@ -2040,14 +2066,28 @@ int launch_pipe2(const KArgs& k0, hipStream_t st) {
     const long per_cu = (160 * 1024) / static_cast<long>(G::LDS) < 4 ? (160 * 1024) / static_cast<long>(G::LDS) : 4;
     if (grid > cus && grid <= per_cu * cus) k.yield_t = CAGPU_PIPE_YIELD_T;
   }
-  std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_pipe_kernel<%d, %d, %s> grid=%u lds=%zu mode=%d%s%s%s", NC, TE,
+  std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_pipe_kernel<%d, %d, %s> grid=%u lds=%zu mode=%d%s%s%s%s", NC, TE,
                 MULTI ? "true" : "false", grid, static_cast<size_t>(G::LDS), k.mode, k.yield_t > 0 ? " fair" : "",
-                k.traj_rows ? " traj" : "", k.fin_obs ? " final" : "");
+                (MULTI && k.env_map) ? " set" : ((k.env_map || k.map.static_bits) ? " map" : ""), k.traj_rows ? " traj" : "",
+                k.fin_obs ? " final" : "");
   if (k.log_rows) std::strncat(g_last_kernel, " log", sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
   if (k.draw_cdf) std::strncat(g_last_kernel, " draw", sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
   // (recording and the final record are template flags: the instantiations without them are the code they were before;
   // the episode log and the policy draw ride on the FINAL instantiations behind uniform tests of their pointers -- no
-  // flags of their own)
+  // flags of their own.  A map set in an n-step launch has one, MSET, on top of FINAL: the only launches that select it)
+  if constexpr (MULTI) {
+    if (k.env_map) {
+      const bool fair = k.yield_t > 0;
+      if (k.traj_rows) {
+        if (fair) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, true, true, true, true, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+        else hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, true, false, true, true, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+      } else if (fair) hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, true, true, false, true, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+      else hipLaunchKernelGGL((pipe::ca_pipe_kernel<NC, TE, true, false, false, true, true>), dim3(grid), dim3(pipe::PNT), G::LDS, st, k);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+      return CA_OK;
+    }
+  }
   if (k.fin_obs || k.log_rows || k.draw_cdf) {
     const bool fair = MULTI && k.yield_t > 0;
     if (k.traj_rows) {
@@ -2111,6 +2151,7 @@ int launch_big(const KArgs& k0, hipStream_t st) {
   const size_t lds = big::lds_bytes(nt);
   std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_big_kernel grid=%ld threads=%d ws_per_wg=%zu mode=%d", wgs, nt, per,
                 k.mode);
+  map_suffix(k);
   if (nt == 1024) {  // 88 KB of LDS: above the default dynamic limit
     static std::atomic<bool> raised[64];
     int dev_id = 0;
@@ -2274,6 +2315,7 @@ struct StepCall {
   const CaFinal* fin = nullptr;
   const CaEpLog* log = nullptr;
   const CaPolicyDraw* draw = nullptr;  // cagpu_step_draw
+  bool maps_multi = false;             // cagpu_step_ex_maps: a map / map set with n_steps > 1 or ring is admitted
   // the record the entry point insists on (the older names: "traj may not be NULL" ...); cagpu_step_ex: none
   enum Need { NEED_NONE, NEED_SET, NEED_TRAJ, NEED_FIN, NEED_LOG } need = NEED_NONE;
   bool query_snapshot = false;   // cagpu_ring_snapshots: answer 1 / 0 instead of launching
@@ -2319,7 +2361,7 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
   if (rc) return rc;
   if (set && (rc = check_map_set(set, "cagpu_step_maps"))) return rc;
   if (n_steps < 1) return fail(CA_EINVAL, "cagpu: n_steps must be >= 1%s");
-  if ((c.map || set) && (n_steps > 1 || c.ring))   // (only cagpu_step_ex can ask for it: the n-step kernels take no map)
+  if ((c.map || set) && (n_steps > 1 || c.ring) && !c.maps_multi)   // (the older names keep refusing: cagpu_step_ex_maps admits it)
     return fail(CA_EINVAL, "%s: a CaMap / CaMapSet with n_steps > 1 or ring (single steps only)", c.who);
   if ((n_steps > 1 || c.ring) && (s->rvo_collab || s->rvo_heading_noise || s->ext_state))
     return fail(CA_EINVAL, "cagpu: CaState.rvo_collab / rvo_heading_noise / ext_state are inputs of ONE step (the caller draws / "
@@ -2338,7 +2380,7 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
     if (c.map->rows < 1 || c.map->cols < 1 || !(c.map->cell > 0.0)) return fail(CA_EINVAL, "cagpu: bad CaMap%s");
     k.map = *c.map;
   }
-  if (set) {  // (single step: the n-step kernels take no set)
+  if (set) {
     k.map = set->map;
     k.env_map = set->env_map;
     k.map_words = static_cast<int64_t>(set->map.rows) * ((set->map.cols + 31) / 32);
@@ -2406,6 +2448,32 @@ int cagpu_step_draw(const CaParams* p, const CaState* s, const CaOut* o, const d
   }
   c.draw = d;
   return step_impl(p, s, o, ext_actions, ar, c, stream);
+}
+
+int cagpu_step_ex_maps(const CaParams* p, const CaState* s, const CaOut* o, const double* ext_actions, const CaAutoReset* ar,
+                       const CaStepEx* x, const CaPolicyDraw* d, void* stream) {
+  StepCall c;
+  c.who = "cagpu_step_ex_maps";
+  c.maps_multi = true;
+  if (x) {
+    c.n_steps = x->n_steps; c.ring = x->ring != 0; c.snapshot_delta = x->snapshot_delta;
+    c.map = x->map; c.set = x->set; c.traj = x->traj; c.fin = x->fin; c.log = x->log;
+  }
+  c.draw = d;
+  return step_impl(p, s, o, ext_actions, ar, c, stream);
+}
+
+int cagpu_map_draw(uint64_t seed, int32_t num_maps, const int64_t* env_ids, const int32_t* counts, int64_t n, int32_t* out,
+                   void* stream) {
+  if (!env_ids || !counts || !out || seed == 0 || num_maps < 1 || n < 0)
+    return fail(CA_EINVAL, "cagpu_map_draw: NULL pointer, seed == 0, num_maps < 1 or n < 0%s");
+  if (n == 0) return CA_OK;
+  const unsigned grid = static_cast<unsigned>((n + 255) / 256);
+  hipLaunchKernelGGL(map_draw_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), seed, num_maps, env_ids, counts,
+                     static_cast<long>(n), out);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
 }
 
 int cagpu_policy_draw(const CaParams* p, const CaState* s, const CaOut* o, const CaAutoReset* ar, const CaPolicyDraw* d,

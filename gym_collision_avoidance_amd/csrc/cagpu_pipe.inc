@@ -236,7 +236,12 @@ struct Geo {
 // FINAL: the instantiation also keeps the final record (CaFinal, KArgs.fin_obs != nullptr) of the envs that auto-reset: wave 0
 // stores the terminal flag words in A4, the S-pair waves save the terminal rows in front of their reset-observation copy.
 // A template flag for the same reason.
-template <int NC, int TE, bool MULTI, bool FAIR = false, bool TRAJ = false, bool FINAL = false>
+// MSET: the n-step form (MULTI) also runs the map-set code of the single-step form -- the per-env grid of A3, the map draw
+// of an auto-reset.  Only a set launch with n_steps > 1 selects it (launch_pipe2, always together with FINAL).  A flag of its
+// own and not a uniform test inside the FINAL instantiations: behind a test the set code cost those kernels -- which
+// map-less launches with the final record, the episode log or the policy draw run -- their register budget (scratch
+// spills inside the step loop at N = 10); with the flag every instantiation without it is the code it was.
+template <int NC, int TE, bool MULTI, bool FAIR = false, bool TRAJ = false, bool FINAL = false, bool MSET = false>
 __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
   static_assert(MULTI || !FAIR, "progress-fair priorities belong to the n-step kernel");
   using G = Geo<NC, TE>;
@@ -744,9 +749,10 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
       }
       // Agent.turning_dir (UnicycleDynamics.py:41-47)
       if (k.s.turning_dir && turned) sh_td[lane] = turning_dir_next(sh_td[lane], heading);
-      // a map set (single-step kernel only; uniform test): the env's grid for the wall tests of A3, its index read by the
-      // env's agent 0 lane (before the wait, which hides the load) and handed to the others
-      const bool wall_set = !MULTI && k.env_map != nullptr;
+      // a map set (the single-step kernel, and the n-step form's MSET instantiations, which only a set launch selects;
+      // uniform test): the env's grid for the wall tests of A3, its index read by the env's agent 0 lane (before the wait,
+      // which hides the load) and handed to the others -- in an n-step launch what the same lane stored at the last auto-reset
+      const bool wall_set = (!MULTI || MSET) && k.env_map != nullptr;
       const uint32_t* wall_bits = nullptr;
       if (wall_set) {
         int m = (active && a == 0) ? k.env_map[env0 + le] : 0;
@@ -860,7 +866,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
               sh_flag[lane] = r.flags;
             }
             // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by its agent 0 lane
-            if (!MULTI && k.map_seed && a == 0) k.env_map[env0 + le] = map_draw(k.map_seed, k.env_id_offset + env0 + le, reset_cnt, k.num_maps);
+            if ((!MULTI || MSET) && k.map_seed && a == 0) k.env_map[env0 + le] = map_draw(k.map_seed, k.env_id_offset + env0 + le, reset_cnt, k.num_maps);
             px = r.px; py = r.py; vx = r.vx; vy = r.vy; heading = r.heading;
             act0 = r.act0; act1 = r.act1; flags = r.flags; step_num = r.step_num;
             sh_gx[lane] = r.gx; sh_gy[lane] = r.gy; sh_ps[lane] = r.ps; sh_rad[lane] = r.rad;

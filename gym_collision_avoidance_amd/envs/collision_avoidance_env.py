@@ -123,7 +123,9 @@ class CollisionAvoidanceEnv(Env):
         self.map = None
         self._map_set = None      # set_static_map(..., per_env=True)
         self.maps = None          # ... one Map per entry of the set
-        self.map_index = None     # ... the device int32 [E] map of every env
+        self._has_map_index = False   # ... `map_index`, the device int32 [E] map of every env, exists (a property)
+        self._map_lazy = False    # sense_map_on_demand(): map sensors when asked for, not after every step
+        self._map_stale = False   # ... and a step came since they were last computed
         self.episode_step_number = None
         self.episode_number = 0
         self.plot_save_dir = None
@@ -304,6 +306,7 @@ class CollisionAvoidanceEnv(Env):
                 self._la_dt_ok = True
             self.episode_step_number += 1
             self._snap = self._obs_np = self._scan_np = None
+            self._map_stale = True   # (a ring runs map batches only with sense_map_on_demand)
             obs, rewards, done, over = sim.step_lookahead()
             info = {"which_agents_done": done, "which_agents_learning": self._learning_info}
             if sim._fin_on:
@@ -318,7 +321,10 @@ class CollisionAvoidanceEnv(Env):
         sim.step(ext, ext_state=self._ext_state)
         self._snap, self._obs_np, self._scan_np = None, None, None
         if Config.USE_STATIC_MAP:
-            self._map_sensors()
+            if self._map_lazy:
+                self._map_stale = True
+            else:
+                self._map_sensors()
         if Config.STORE_HISTORY and self.num_envs == 1:
             self._record_history()
         if self.num_envs > 1:
@@ -679,14 +685,12 @@ class CollisionAvoidanceEnv(Env):
                     bool(self._host_dynamics) or bool(self._hostdyn_by_env and any(self._hostdyn_by_env)))
         sim.fresh_outputs = E > 1 and not self.zero_copy and not nets and not host_any
         # the look-ahead ring (see __init__): every policy answered inside the step kernel, nothing between two steps
-        ring = self.lookahead
-        if ring is None:
-            # (with the final record every slot carries its final block as well: the same budget, a shorter ring)
-            slot_bytes = E * N * (4 * sim.W + 5) + E + (sim.final_step_bytes if sim._fin_on else 0)
-            ring = int(min(self.LOOKAHEAD_MAX, max(8, self.LOOKAHEAD_BYTES // slot_bytes)))
-        self._la_on = bool(self._policy_pool is None and   # (a draw: the learning mask of every step is read from the state)
-                           E > 1 and ring > 0 and not nets and not host_any and not Config.USE_STATIC_MAP and
-                           not any(a.policy.is_external for g in groups for a in g) and sim.lookahead_ok())
+        ring = self._ring_len(sim)
+        # (a static map: the env scans after every step, so its ring stays off -- unless sense_map_on_demand() defers the scans)
+        self._la_but_map = bool(self._policy_pool is None and   # (a draw: the learning mask of every step is read from the state)
+                                E > 1 and ring > 0 and not nets and not host_any and
+                                not any(a.policy.is_external for g in groups for a in g) and sim.lookahead_ok())
+        self._la_on = self._la_but_map and (not Config.USE_STATIC_MAP or self._map_lazy)
         sim.enable_lookahead(ring if self._la_on else 0, fresh=not self.zero_copy, adaptive=True)
         self._la_dt_ok = sim.p.dt == self.dt_nominal
         if self._la_on:
@@ -703,7 +707,7 @@ class CollisionAvoidanceEnv(Env):
                         num_to_store=Config.LASERSCAN_NUM_PAST, env_map=idx)
             sim.set_map_seed(key)
             self.map = maps[int(idx[0])]
-            self.map_index = sim.env_map
+            self._has_map_index = True
             self._map_sensors(groups)
         elif Config.USE_STATIC_MAP:  # collision_avoidance_env.py:273-274, :378-392: Map(16 m, 16 m, 0.1 m)
             sm = self.static_map_filename
@@ -815,8 +819,37 @@ class CollisionAvoidanceEnv(Env):
 
     def _scan_host(self):
         if self._scan_np is None:
+            self._map_fresh()
             self._scan_np = self._sim.scan.cpu().numpy()
         return self._scan_np
+
+    def _map_fresh(self):
+        """sense_map_on_demand: the map sensors of the step last handed out, computed now if a step came since"""
+        if self._map_stale and self._sim is not None and Config.USE_STATIC_MAP:
+            self._map_sensors()
+
+    def sense_map_on_demand(self, on=True):
+        """Opt-in for Config.USE_STATIC_MAP batches: compute the map sensors (laser scan, occupancy windows) when
+        `env.laserscan`, `env.occupancy_grid` or an observation dict asks for them, not after every step.  The scan
+        history (LASERSCAN_NUM_PAST rows) then counts those requests instead of the steps.  With every policy internal
+        nothing is left to do between two steps, so step(None) is served from the look-ahead ring (see __init__) -- walls
+        and map draws are those of single steps; a request rewinds the ring to the step last handed out, and so does reading
+        `env.map_index` (the maps of the step last handed out, not those the ring has drawn ahead).  Off by default:
+        the env scans after every step and its ring stays off under a static map."""
+        on = bool(on)
+        if on == self._map_lazy:
+            return
+        self._map_lazy = on
+        if self._sim is None or not Config.USE_STATIC_MAP:
+            return
+        sim = self._sim
+        sim.sync()
+        if not on:
+            self._map_fresh()
+        self._la_on = self._la_but_map and on
+        sim.enable_lookahead(self._ring_len(sim) if self._la_on else 0, fresh=not self.zero_copy, adaptive=True)
+        if self._la_on:
+            self._learning_info = {a.id: a.policy.is_still_learning for a in self.agents}
 
     def _map_sensors(self, groups=None):
         """the map sensors of the current state: the laser scan, and the OccupancyGridSensor windows where some agent of
@@ -835,10 +868,13 @@ class CollisionAvoidanceEnv(Env):
                 sim.set_occupancy_grid(x_width=xw, y_width=yw)
         sim.laserscan()
         self._occ_np = None
+        self._scan_np = None
         if sim.occ is not None:
             sim.occupancy_grid()
+        self._map_stale = False
 
     def _occ_host(self):
+        self._map_fresh()
         if self._occ_np is None:
             self._occ_np = self._sim.occ.cpu().numpy()
         return self._occ_np
@@ -922,15 +958,28 @@ class CollisionAvoidanceEnv(Env):
         self.max_possible_reward = float(np.max(self.possible_reward_values))
 
     @property
+    def map_index(self):
+        """device int32 [E]: the map of every env of a map set (set_static_map(per_env=True); None otherwise), at the step
+        last handed out -- with the look-ahead ring on (sense_map_on_demand) reading it rewinds a ring that has run ahead,
+        whose auto-resets have already drawn the maps of episodes not handed out yet"""
+        return self._sim.env_map if (self._has_map_index and self._sim is not None) else None
+
+    @property
     def laserscan(self):
         """float32 device tensor [E, N, LASERSCAN_NUM_PAST, LASERSCAN_LENGTH] (Config.USE_STATIC_MAP only)."""
-        return None if self._sim is None else self._sim.scan
+        if self._sim is None:
+            return None
+        self._map_fresh()
+        return self._sim.scan
 
     @property
     def occupancy_grid(self):
         """bool device tensor [E, N, H, W]: every agent's OccupancyGridSensor window of the current state (H x W =
         y_width x x_width in map cells); None unless some agent of the batch lists the sensor."""
-        return None if self._sim is None else self._sim.occ
+        if self._sim is None:
+            return None
+        self._map_fresh()
+        return self._sim.occ
 
     # ------------------------------------------------------------------ trajectories (core.BatchedSim.record_trajectories)
     def record_trajectories(self, on=True, max_bytes=None):
@@ -1165,7 +1214,8 @@ class CollisionAvoidanceEnv(Env):
         slots); `total_time_to_goal`, `collision`, `all_at_goal`, `any_stuck`, `outcome` ("collision" / "all_at_goal" /
         "stuck") [M] -- and `dropped`, the number of episodes that ended but were overwritten before this call (int).
         `env` is this shard's env index (add env_id_offset for the global one).  Does not rewind the look-ahead ring.
-        With measure_episodes() on, additionally `path_length`, `min_gap`, `turn_sum`, `min_gap_t` [M, N] float64 (NaN where
+        With per-env maps (set_static_map(per_env=True)), additionally `map` [M]: the `map_index` value the env held
+        while the episode ran.  With measure_episodes() on, additionally `path_length`, `min_gap`, `turn_sum`, `min_gap_t` [M, N] float64 (NaN where
         the record has no metrics) and `moved_steps`, `close_steps`, `min_gap_partner` [M, N] int32 (-1 there), filled for
         every record whose (env, episode) is in the metrics' drain as well, `has_metrics` [M] bool saying which, and
         `metrics_dropped` (int)."""
@@ -1174,6 +1224,8 @@ class CollisionAvoidanceEnv(Env):
         from gym_collision_avoidance_amd import episodes as eplog
         ep = self._sim.episodes()
         out = eplog.suite_columns({k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in ep.items()})
+        if "map" in ep:   # a map set: the map_index value the env held while the episode ran (-1: not known any more)
+            out["map"] = ep["map"].cpu().numpy().astype(np.int64)
         if self._sim._met is not None:
             from gym_collision_avoidance_amd import episode_metrics as epmet
             met = self.episode_metrics()
@@ -1190,14 +1242,19 @@ class CollisionAvoidanceEnv(Env):
             out["metrics_dropped"] = int(met["dropped"])
         return out
 
+    def _ring_len(self, sim):
+        """the longest look-ahead ring: `lookahead` if given, else what the byte budget holds of the batch's slots (with the
+        final record every slot carries its final block as well: the same budget, a shorter ring)"""
+        if self.lookahead is not None:
+            return self.lookahead
+        slot_bytes = self.num_envs * sim.N * (4 * sim.W + 5) + self.num_envs + (sim.final_step_bytes if sim._fin_on else 0)
+        return int(min(self.LOOKAHEAD_MAX, max(8, self.LOOKAHEAD_BYTES // slot_bytes)))
+
     def _resize_ring(self):
-        """the default ring length follows the bytes of a slot (see _upload): recomputed when the final record is toggled"""
-        sim = self._sim
+        """the default ring length follows the bytes of a slot: recomputed when the final record is toggled"""
         if not self._la_on or self.lookahead is not None:
             return
-        slot_bytes = self.num_envs * sim.N * (4 * sim.W + 5) + self.num_envs + (sim.final_step_bytes if sim._fin_on else 0)
-        sim.enable_lookahead(int(min(self.LOOKAHEAD_MAX, max(8, self.LOOKAHEAD_BYTES // slot_bytes))),
-                             fresh=not self.zero_copy, adaptive=True)
+        self._sim.enable_lookahead(self._ring_len(self._sim), fresh=not self.zero_copy, adaptive=True)
 
     def _final_items(self, info, over, final_obs, final_flags):
         """adds "final_observation" / "final_info" to `info` -> truncated [E] (a few elementwise device ops, no sync)"""
@@ -1227,8 +1284,11 @@ class CollisionAvoidanceEnv(Env):
         self.episode_step_number += int(n_steps)
         sim.rollout(int(n_steps))
         self._snap, self._obs_np, self._scan_np = None, None, None
-        if Config.USE_STATIC_MAP:
-            self._map_sensors()
+        if Config.USE_STATIC_MAP:   # (once, on the final state: the scan kernel reads the current state)
+            if self._map_lazy:
+                self._map_stale = True
+            else:
+                self._map_sensors()
         info = {"which_agents_done": sim.done.bool() if self.num_envs > 1 else
                 {a.id: bool(d) for a, d in zip(self.agents, sim.done[0].cpu().numpy())},
                 "which_agents_learning": {a.id: a.policy.is_still_learning for a in self.agents}}

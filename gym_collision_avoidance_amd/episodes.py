@@ -86,6 +86,25 @@ def gather(rows, head, env, k, slot):
             "flags": flag_words(r[..., ROW_FLAGS])}
 
 
+def map_column(k, given_ep, given_map, key_from, keyed, drawn):
+    """Which map of a map set did an episode run on?  All arguments per record [M]: k the episode's index, given_ep /
+    given_map the episode the env was in when the host last GAVE it a map (reset, set_env_map) and that map, key_from the
+    first episode whose map was decided under the key now in force (0: since the env's reset; a key replaced while the env
+    was in episode c: c + 1), keyed whether that key is != 0, drawn the draw of (key, env, k) -- CaMapSet.map_seed's rule,
+    read only where it applies.  The episode an env was given its map in ran on that map; a later one on its draw, or,
+    without a key, still on the given map -- both only if the key in force has been since that episode's map was decided.
+    Everything else is -1: the index cannot be known, and a wrong one is never reported.  -> int64 [M]"""
+    k, given_ep, key_from = _i64(k), _i64(given_ep), _i64(key_from)
+    given_map, drawn = _i64(given_map), _i64(drawn)
+    unknown = k * 0 - 1
+    later = (k > given_ep) & (k >= key_from)
+    if keyed:
+        after = _where(later, drawn, unknown)
+    else:   # no draws since episode key_from - 1: the given map still holds if it was given in or after that episode
+        after = _where(later & (key_from <= given_ep + 1), given_map, unknown)
+    return _where(k == given_ep, given_map, after)
+
+
 def drain(rows, head, cursor, rc):
     """select() + gather(): -> (dict of the new episodes + "dropped", new_cursor)"""
     env, k, slot, dropped, new_cursor = select(head, cursor, rc)

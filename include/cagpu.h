@@ -444,8 +444,8 @@ typedef struct CaStepEx {
  *            cols >= 1 and cell > 0.
  *   set      a map per env (CaMapSet; cagpu_step_maps has the semantics): set->env_map or set->map.static_bits NULL,
  *            num_maps < 1 or a bad geometry is rejected.
- *            map and set at once is rejected.  Either of them with n_steps > 1 or ring is rejected: the n-step kernels take
- *            no map, and no older entry point reaches such a launch.
+ *            map and set at once is rejected.  Either of them with n_steps > 1 or ring is rejected by cagpu_step_ex,
+ *            cagpu_step_draw and every older name; cagpu_step_ex_maps (below) is the same call with that one rule lifted.
  *   traj     the trajectory tape (CaTraj): step t of the call records slot t.  traj->rows NULL or not 16-byte aligned, or
  *            traj->episode not 4-byte aligned, is rejected.
  *   fin      the final record (CaFinal) of every env that auto-resets.  fin->obs NULL or not 16-byte aligned,
@@ -464,6 +464,31 @@ typedef struct CaStepEx {
  * records bit for bit. */
 int cagpu_step_ex(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                   const CaStepEx *x, void *stream);
+
+/* MAPS IN FUSED LAUNCHES (additive to v12; no new struct).  cagpu_step_draw (cagpu_step_ex when draw == NULL) in every rule
+ * but one: x->map or x->set is admitted with n_steps > 1 and with ring.  Map and set at once, a bad CaMapSet and the
+ * per-step inputs (rvo_collab / rvo_heading_noise / ext_state) in a multi-step call are rejected as there.
+ *   ordering   step t of the launch tests its walls against the map the env holds when step t begins.  An auto-reset in step
+ *              t with set->map_seed != 0 stores the env's next map (CaMapSet.map_seed: a function of the key, the global env
+ *              id and the env's reset count) AFTER that test: the terminal step sees the old map, step t + 1 the new one --
+ *              n single cagpu_step_maps calls, bit for bit.  An index outside [0, num_maps) reads no map memory and raises
+ *              bit 2 of the fault word in every step that meets it.
+ *   kernels    the kernel choice does not depend on the map: cagpu_ring_snapshots() answers for a ring launch with a map
+ *              or a set what it answers without one.  env_map is NOT part of a ring's rewind snapshot (the state slab): a
+ *              caller who rewinds a ring of a set with a key restores its own copy of env_map, taken before the launch.
+ *              A set in an n-step launch runs the MSET instantiations of the pipelined and the general kernel, which no other
+ *              launch selects (cagpu_last_kernel() shows " set"); a rollout that is split into single launches and the
+ *              large-env kernel carry the map or set into every launch (" map", as for every single step with a map or set).
+ *   sensors    cagpu_laserscan / cagpu_occupancy_grid read the CURRENT state: after an n-step launch that is the final one. */
+struct CaPolicyDraw;   /* (defined with cagpu_step_draw below) */
+int cagpu_step_ex_maps(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
+                       const CaStepEx *x, const struct CaPolicyDraw *draw /* may be NULL */, void *stream);
+
+/* out[i] = the map a map-set env with global id env_ids[i] takes at its counts[i]-th auto-reset under key `seed`
+ * (CaMapSet.map_seed's rule), i < n: device int64 / int32 in, device int32 out.  Lets a host say which map a logged episode
+ * ran on without a field in the log record.  CA_EINVAL: NULL pointers, seed == 0, num_maps < 1, n < 0.  n == 0: nothing. */
+int cagpu_map_draw(uint64_t seed, int32_t num_maps, const int64_t *env_ids, const int32_t *counts, int64_t n, int32_t *out,
+                   void *stream);
 
 /* = cagpu_step_ex with x == NULL (n_steps = 1, no ring, no record). */
 int cagpu_step(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
@@ -488,7 +513,7 @@ int cagpu_laserscan(const CaParams *p, const CaState *s, const CaMap *map, const
  * env_map[e].  With set->map_seed != 0 an auto-reset draws the env's next map (CaMapSet.map_seed); the wall test of the
  * terminal step still uses the old map, the next step and the next scan the new one (the reference's reset observation
  * already sees the new map).  Envs with more than 64 agents, the pipelined and the plain step kernels all take a set; the
- * n-step kernels do not.  cagpu_step_maps = CaStepEx{n_steps = 1, set}; additionally `set` may not be NULL.
+ * n-step kernels do through cagpu_step_ex_maps only.  cagpu_step_maps = CaStepEx{n_steps = 1, set}; additionally `set` may not be NULL.
  * cagpu_laserscan_maps: CA_EINVAL, nothing launched, for a NULL set and for what cagpu_step_ex rejects of a set. */
 int cagpu_step_maps(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                     const CaMapSet *set, void *stream);
