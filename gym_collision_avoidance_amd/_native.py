@@ -4,7 +4,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# CAGPU_LIB: load another build of the same ABI (the -DCAGPU_ABLATE experiment build of scratch/); the library itself
+# CAGPU_LIB: load another build of the same ABI (a parent commit's library for a same-box comparison); the library itself
 # reads no environment variable
 LIB_PATH = os.environ.get("CAGPU_LIB") or os.path.join(HERE, "libcagpu.so")
 

@@ -28,31 +28,12 @@ def needs_build():
     return any(os.path.getmtime(d) > t for d in source_files())
 
 
-def build(force=False, verbose=False, variant=None):
-    """variant None: the product library libcagpu.so.  variant "knobs" / "ablate": an EXPERIMENT build next to it
-    (libcagpu_knobs.so / libcagpu_ablate.so, -DCAGPU_KNOBS / -DCAGPU_ABLATE: geometry overrides from CAGPU_* environment
-    variables, in-kernel phase timers), loaded only by scratch/ scripts through CAGPU_LIB; never the product file."""
-    if variant is None and not force and not needs_build():
+def build(force=False, verbose=False):
+    """the product library libcagpu.so, rebuilt when a source is newer than it (or when forced)"""
+    if not force and not needs_build():
         return OUT
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    out = OUT if variant is None else os.path.join(HERE, "libcagpu_%s.so" % variant)
-    # "ablate_fast" / "knobs_fast": the same with only the N = 10 unstaged instantiations compiled (quick iterations)
-    # "exp<mask>_fast": compile-time experiment switches, -DCAGPU_EXP=<mask> (see EXP() in cagpu.hip)
-    # and "dKEY=VAL" -> -DCAGPU_KEY=VAL; tokens are separated by "_", or by "," when a KEY itself contains "_"
-    # (e.g. "dPIPE_WT=0,fast" -> -DCAGPU_PIPE_WT=0 -DCAGPU_FAST)
-    # "fFLAG" tokens pass an -mllvm option through (compiler experiments), e.g. famdgpu-enable-max-ilp-scheduling-strategy
-    extra = [] if variant is None else [("-DCAGPU_EXP=%s" % v[3:]) if v.startswith("exp") else
-                                        ("-mllvm=-%s" % v[1:]) if (v.startswith("f") and v not in ("fast",)) else
-                                        ("-DCAGPU_%s" % v[1:]) if (v.startswith("d") and "=" in v) else
-                                        "-DCAGPU_%s" % v.upper() for v in
-                                        (variant.split(",") if "," in variant or "=" in variant else variant.split("_"))]
-    extra = [y for x in extra for y in (["-mllvm", x[len("-mllvm="):]] if x.startswith("-mllvm=") else [x])]
-    cmd = [hipcc] + FLAGS + extra + [SRC, "-o", out]
-    if variant is not None:
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-        return out
+    cmd = [hipcc] + FLAGS + [SRC, "-o", OUT]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -115,5 +96,4 @@ def build_info():
 
 
 if __name__ == "__main__":
-    import sys
-    build(force=True, verbose=True, variant=sys.argv[1] if len(sys.argv) > 1 else None)
+    build(force=True, verbose=True)

@@ -74,7 +74,7 @@ struct KArgs {
   int64_t ring_obs, ring_agent, ring_env;
   // cagpu_rollout_ring: != 0: the pipelined n-step kernel also stores the state it starts from at (address + snap_delta)
   int64_t snap_delta;
-  int32_t ablate;  // timing experiments only (-DCAGPU_ABLATE + env CAGPU_ABLATE); 0 in product builds
+  int32_t reserved0;  // always 0, read by nobody: keeps the kernarg offsets of the members after it
   int32_t launch_seq;  // a per-process launch counter: tags the words of the n-step kernel's per-CU progress table (cagpu_pipe.inc)
   float inv_h_f, inv_dt_f;  // pipelined kernels: 1.0f / float(p.rvo_time_horizon), 1.0f / float(p.rvo_dt) -- IEEE float quotients, set by launch_pipe2
   int32_t yield_t;     // > 0: progress-fair priorities among the workgroups of a CU (PIPE_PRIO in cagpu_pipe.inc); set by launch_pipe2
@@ -188,10 +188,6 @@ __device__ __forceinline__ float sqrtf_rn(float a) { return sqrtf(a); }
 // ORCA's operands are velocities, positions and their differences -- 0 (handled: 0 / b = 0, sqrt(0) = 0) or 1e-16 .. 1e8
 // in magnitude.  The stand-alone cagpu_orca kernel keeps the compiler's `/` and sqrtf for arbitrary inputs, and both
 // are held to the same oracle bit for bit (tests/test_gpu_parity.py).
-#if defined(CAGPU_EXP) && (CAGPU_EXP & 4)
-__device__ __forceinline__ float divq(float a, float b) { return a / b; }
-__device__ __forceinline__ float sqrtq(float a) { return sqrtf(a); }
-#else
 __device__ __forceinline__ float divq(float a, float b) {
   float y = __builtin_amdgcn_rcpf(b);
   const float e = __builtin_fmaf(-b, y, 1.0f);
@@ -210,15 +206,10 @@ __device__ __forceinline__ float sqrtq(float x) {
   o = (r_up > 0.0f) ? s_up : o;
   return (x == 0.0f) ? x : o;
 }
-#endif
 // ... and for float64 (distances, preferred velocity, ego frame: UnicycleDynamics / Dynamics / the sensor): the compiler's
 // sequences are rsq + 9 multiply-adds (square root) and rcp + 2 Newton steps + one residual correction (divide); the range
 // handling around them (v_ldexp / v_cmp_class / v_div_scale / v_div_fixup) costs 8 and 3 more instructions per call.
 // scratch/divsqrt_check.hip: identical bits on 2^28 random operands with exponents in [-300, 300] / [-600, 600].
-#if defined(CAGPU_EXP) && (CAGPU_EXP & 4)
-__device__ __forceinline__ double divd(double a, double b) { return a / b; }
-__device__ __forceinline__ double sqrtd(double a) { return sqrt(a); }
-#else
 __device__ __forceinline__ double divd(double a, double b) {
   double y = __builtin_amdgcn_rcp(b);
   y = __builtin_fma(__builtin_fma(-b, y, 1.0), y, y);
@@ -236,7 +227,6 @@ __device__ __forceinline__ double sqrtd(double x) {
   g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
   return (x == 0.0) ? x : g;
 }
-#endif
 // RVO2's Vector2 / float: multiply by the reciprocal
 __device__ __forceinline__ F2 over(F2 a, float s) { const float inv = divf(1.0f, s); return f2(a.x * inv, a.y * inv); }
 __device__ __forceinline__ F2 unitf(F2 a) { return over(a, sqrtf_rn(dotf(a, a))); }
@@ -596,57 +586,18 @@ constexpr int ROW = 64;
 // slots -- the half-plane store Lmat[rank * CS + agent] of the ORCA phase: a stride of 64 float4 put all nine of them on
 // the same four banks (SQ_LDS_BANK_CONFLICT 767 k cycles per launch at 4096 x 10, profiles/r02_rocprof_summary.md) --
 // spread over the banks, while lanes that walk agents for a fixed slot stay consecutive.
-#ifndef CAGPU_CSPAD
-#define CAGPU_CSPAD 1
-#endif
-constexpr int CS_ROW = ROW + CAGPU_CSPAD;
+constexpr int CS_ROW = ROW + 1;
 constexpr int KEY_NONE = 2147483647;  // sort key of a pair that is not sensed (self, beyond the sensing horizon)
-#ifdef CAGPU_ABLATE  // experiment build (scratch/): run-time switches in k.ablate + in-kernel phase timers
-#define AB(bit) (k.ablate & (bit))
-#define DUP(bit) for (int rep_ = 0; rep_ < ((k.ablate & (bit)) ? 2 : 1); ++rep_)  // run an idempotent phase twice: its cost in situ
-__device__ unsigned long long g_prof[16];
-__device__ unsigned long long g_wgprof[1024 * 16];
-#define TICK(slot) do { if (tid == 0) { const unsigned long long now_ = clock64(); sh_prof[slot] += now_ - tprev_; tprev_ = now_; } } while (0)
-#else
-#define AB(bit) false
-#define DUP(bit)
-#if defined(CAGPU_WGTIME)
-// product-like build with one wall-clock stamp (100 MHz) per phase boundary on thread 0: g_wgphase[wg][slot] += elapsed
-__device__ unsigned int g_wgphase[4096 * 16];
-#define TICK(slot) do { if (tid == 0) { const unsigned long long now_ = wall_clock64(); wg_ph[slot] += static_cast<unsigned>(now_ - wg_prev); wg_prev = now_; } } while (0)
-#else
-#define TICK(slot) do {} while (0)
-#endif
-#endif
-#ifdef CAGPU_WGTIME  // experiment build: per-workgroup wall-clock stamps of the LAST launch (100 MHz counter), no timers inside
-__device__ unsigned long long g_wgtime[4096 * 8];
-#endif
-// Compile-time experiment switches (scratch/ builds: -DCAGPU_EXP=<bit mask>, libcagpu_exp<mask>_fast.so); 0 in the product
-#ifndef CAGPU_EXP
-#define CAGPU_EXP 0
-#endif
-#define EXP(bit) (((CAGPU_EXP) & (bit)) != 0)
 #define LP1_UNROLL _Pragma("unroll")
-// Workgroup barrier between phases that exchange data through LDS only: waits for this wave's LDS traffic, not for its
-// outstanding global stores (__syncthreads() = workgroup fence + barrier also drains vmcnt, i.e. every observation
-// store has to be acknowledged by the L2 before the phase after it may start).
-#if (CAGPU_EXP & 2)
-#define WG_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#else
+// Workgroup barrier between phases that exchange data through LDS.
 #define WG_SYNC() __syncthreads()
-#endif
 // Wave priorities per phase (s_setprio 0..3).  Four workgroups share a CU, so every SIMD holds one wave of each of them,
 // usually in different phases.  The agent wave's serial chains (one lane per agent: they are what the workgroup's other
-// three waves are waiting for) and the linearProgram3 stragglers issue first, then pair phases in the order of the
-// step (a workgroup that is behind overtakes one that is ahead): 21.6 -> 20.3 us per step, rollout 14.1 -> 12.6
-// (profiles/r02_kernel_geometry.md).  PRIO(...) lists the level of a phase under schemes 1 .. 8 (-DCAGPU_PRIO=<n>; 0 =
-// hardware default): 1 agent wave 3 / ORCA pairs 2 / sensor pairs 1; 2 only linearProgram3 raised; 3 "earlier phase =
-// higher"; 4 agent wave 3, everything else 1; **5 = 1 with the emission phase and the post-linearProgram3 wait at 0 (the
-// product)**; 6 - 8 variations of 5 (sensor phases one level up; ORCA pairs at 3; emission at 1), all 0.05 - 0.3 us behind 5.
-#ifndef CAGPU_PRIO
-#define CAGPU_PRIO 5
-#endif
-#define PRIO(a, b, c, d, e, ...) do { constexpr int pr_[] = {0, a, b, c, d, e, __VA_ARGS__}; if (CAGPU_PRIO) __builtin_amdgcn_s_setprio(pr_[CAGPU_PRIO]); } while (0)
+// three waves are waiting for) and the linearProgram3 stragglers issue first (3), then pair phases in the order of the
+// step (a workgroup that is behind overtakes one that is ahead: ORCA pairs 2, sensor pairs 1), the emission phase and the
+// post-linearProgram3 wait last (0): 21.6 -> 20.3 us per step, rollout 14.1 -> 12.6 (profiles/r02_kernel_geometry.md).
+// Variations (sensor phases one level up; ORCA pairs at 3; emission at 1) all measured 0.05 - 0.3 us behind.
+#define PRIO(level) __builtin_amdgcn_s_setprio(level)
 // Pair items w = 0 .. n_items-1 are dealt to the NT threads in rounds; odd rounds run BACKWARDS over the threads, so the
 // last, partial round lands on the highest waves and wave 0 -- the agent wave -- is free for its one-lane-per-agent work
 // while the other waves finish the pair phase (400 items on 256 threads: wave 0 has one round, waves 2 and 3 two).
@@ -922,18 +873,6 @@ __global__ __launch_bounds__(NT, MULTI ? (NC == 20 ? 2 : 4) : 1) void ca_kernel(
     }
   }
 
-#ifdef CAGPU_ABLATE
-  __shared__ unsigned long long sh_prof[16];
-  if (tid < 16) sh_prof[tid] = 0;
-  __syncthreads();
-  unsigned long long tprev_ = clock64();
-#endif
-#ifdef CAGPU_WGTIME
-  unsigned long long wg_t0 = 0, wg_info = 0, wg_lp3 = 0, wg_prev = 0;
-  unsigned wg_ph[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long wg_c0 = 0;
-  if (tid == 0) { wg_t0 = wg_prev = wall_clock64(); wg_c0 = clock64(); }
-#endif
   // The phases are straight-line code in the single-step kernel (lambdas inlined at their call sites): with the
   // n-step loop and the two-pass sensing loop around them the register allocator keeps ~100 more VGPRs alive around
   // the back edges (profiles/r01_kernel_geometry.md).  MULTI = true keeps the step loop for cagpu_rollout.
@@ -951,13 +890,12 @@ __global__ __launch_bounds__(NT, MULTI ? (NC == 20 ? 2 : 4) : 1) void ca_kernel(
     const bool active = wave0 && (lane < tile_n) && (e < p.num_envs);
     const int ebase = active ? le * N : 0;
     const long i = e * N + a;
-    TICK(0);
     if (k.mode == MODE_STEP) {
       // ================= A1: who queries ORCA, float bodies (RVOPolicy.py:57-74)
       const uint32_t pol = (r.flags >> CA_POLICY_SHIFT) & 0xF;
       const bool query = active && !(r.flags & CA_DONE);  // env.py:311
       const bool rvo = query && pol == CA_POL_RVO;
-      if (wave0) PRIO(3, 0, 3, 3, 3, 3, 3, 3); else PRIO(2, 0, 3, 1, 2, 2, 3, 2);
+      if (wave0) PRIO(3); else PRIO(2);
       if (wave0) {
         ep_step += 1;  // env.py:183
         // (an absent slot of a ragged batch sits at infinity: distSq = inf = "not a neighbour" for everybody)
@@ -976,109 +914,105 @@ __global__ __launch_bounds__(NT, MULTI ? (NC == 20 ? 2 : 4) : 1) void ca_kernel(
         }
       }
       WG_SYNC();
-      TICK(1);
       F2 v_orca = f2(0.f, 0.f);  // this lane's ORCA velocity (agent wave)
-      PRIO(2, 0, 3, 1, 2, 2, 3, 2);
-      if (!AB(1)) {
-        // ================= P2: every (querying agent, other) pair: neighbour rank (ascending distSq, ties by index:
-        // Agent::insertAgentNeighbor) + ORCA half-plane
-        const float range_sq = sqf(static_cast<float>(p.sensing_horizon));
-        const bool unlimited = !(range_sq < INFINITY);
-        const float inv_h = divf(1.0f, static_cast<float>(p.rvo_time_horizon));
-        const float inv_dt = divf(1.0f, static_cast<float>(p.rvo_dt));  // RVOPolicy.py:13,26
-        const float collab = static_cast<float>(p.rvo_collab_coeff);
-        const int n_live = sh_q3[ROW + 1];
-        // A wave holds WHOLE agents -- floor(64 / (N - 1)) of them, lane = (agent, one of its N - 1 others) -- so a lane
-        // gets the other distances of its agent from its neighbour lanes (ds_bpermute: no recomputation, no LDS round
-        // trip) and counts its rank.  At N = 10: 7 agents per wave, 28 per round of the workgroup.
-        constexpr int NW = NT / 64;
-        const int wv = tid >> 6, wl = tid & 63;
-        const int GN = NC ? (NC > 1 ? NC - 1 : 1) : (N > 1 ? N - 1 : 1);  // lanes per agent
-        const float inv_gn = 1.0f / static_cast<float>(GN);
-        const int apw = 64 / GN;     // agents per wave
-        const int apr = NW * apw;    // agents per round of the workgroup
-        const int g = div_small<(NC > 1 ? NC - 1 : NC)>(wl, inv_gn), jo = wl - __mul24(g, GN);
-        const int gbase = (wl - jo) << 2;  // ds_bpermute byte address of the first lane of my agent's group
+      PRIO(2);
+      // ================= P2: every (querying agent, other) pair: neighbour rank (ascending distSq, ties by index:
+      // Agent::insertAgentNeighbor) + ORCA half-plane
+      const float range_sq = sqf(static_cast<float>(p.sensing_horizon));
+      const bool unlimited = !(range_sq < INFINITY);
+      const float inv_h = divf(1.0f, static_cast<float>(p.rvo_time_horizon));
+      const float inv_dt = divf(1.0f, static_cast<float>(p.rvo_dt));  // RVOPolicy.py:13,26
+      const float collab = static_cast<float>(p.rvo_collab_coeff);
+      const int n_live = sh_q3[ROW + 1];
+      // A wave holds WHOLE agents -- floor(64 / (N - 1)) of them, lane = (agent, one of its N - 1 others) -- so a lane
+      // gets the other distances of its agent from its neighbour lanes (ds_bpermute: no recomputation, no LDS round
+      // trip) and counts its rank.  At N = 10: 7 agents per wave, 28 per round of the workgroup.
+      constexpr int NW = NT / 64;
+      const int wv = tid >> 6, wl = tid & 63;
+      const int GN = NC ? (NC > 1 ? NC - 1 : 1) : (N > 1 ? N - 1 : 1);  // lanes per agent
+      const float inv_gn = 1.0f / static_cast<float>(GN);
+      const int apw = 64 / GN;     // agents per wave
+      const int apr = NW * apw;    // agents per round of the workgroup
+      const int g = div_small<(NC > 1 ? NC - 1 : NC)>(wl, inv_gn), jo = wl - __mul24(g, GN);
+      const int gbase = (wl - jo) << 2;  // ds_bpermute byte address of the first lane of my agent's group
 #pragma unroll
-        for (int c0 = 0; c0 < (NC ? tile_n : n_live); c0 += apr) {
-          if (c0 >= n_live) continue;  // workgroup-uniform
-          const int c = c0 + wv * apw + g;
-          const bool valid = (g < apw) && (c < n_live);
-          const int ag = sh_q[valid ? c : 0];
-          const int eb = __mul24(div_small<NC>(ag, inv_n), N), aa = ag - eb;
-          const int j = jo + ((jo >= aa) ? 1 : 0);  // my other agent (index order is kept: ties by index)
-          const F2 mpos = f2(sh_fpx[ag], sh_fpy[ag]);
-          float dj = INFINITY;
-          if (valid && j < N) {
-            const F2 d = mpos - f2(sh_fpx[eb + j], sh_fpy[eb + j]);
-            dj = dotf(d, d);
-            if (!unlimited && !(dj < range_sq)) dj = INFINITY;
-          }
-          // rank = number of others that are closer (ties by index: they need two floats to be EQUAL -- symmetric starts --
-          // and are settled in a second walk by the waves that hold one)
-          int rank = 0, cnt = (N > 1) ? N - 1 : 0, tie = 0;
+      for (int c0 = 0; c0 < (NC ? tile_n : n_live); c0 += apr) {
+        if (c0 >= n_live) continue;  // workgroup-uniform
+        const int c = c0 + wv * apw + g;
+        const bool valid = (g < apw) && (c < n_live);
+        const int ag = sh_q[valid ? c : 0];
+        const int eb = __mul24(div_small<NC>(ag, inv_n), N), aa = ag - eb;
+        const int j = jo + ((jo >= aa) ? 1 : 0);  // my other agent (index order is kept: ties by index)
+        const F2 mpos = f2(sh_fpx[ag], sh_fpy[ag]);
+        float dj = INFINITY;
+        if (valid && j < N) {
+          const F2 d = mpos - f2(sh_fpx[eb + j], sh_fpy[eb + j]);
+          dj = dotf(d, d);
+          if (!unlimited && !(dj < range_sq)) dj = INFINITY;
+        }
+        // rank = number of others that are closer (ties by index: they need two floats to be EQUAL -- symmetric starts --
+        // and are settled in a second walk by the waves that hold one)
+        int rank = 0, cnt = (N > 1) ? N - 1 : 0, tie = 0;
+        for_n<8>(GN, [&](const int q) {
+          const float dq = __int_as_float(__builtin_amdgcn_ds_bpermute(gbase + 4 * q, __float_as_int(dj)));
+          rank += static_cast<int>(dq < dj);
+          tie += static_cast<int>(dq == dj);
+        });
+        if (__any(tie > 1 && dj < INFINITY)) {  // (a distance always equals itself)
           for_n<8>(GN, [&](const int q) {
             const float dq = __int_as_float(__builtin_amdgcn_ds_bpermute(gbase + 4 * q, __float_as_int(dj)));
-            rank += static_cast<int>(dq < dj);
-            tie += static_cast<int>(dq == dj);
+            rank += static_cast<int>(dq == dj) & static_cast<int>(q < jo);
           });
-          if (__any(tie > 1 && dj < INFINITY)) {  // (a distance always equals itself)
-            for_n<8>(GN, [&](const int q) {
-              const float dq = __int_as_float(__builtin_amdgcn_ds_bpermute(gbase + 4 * q, __float_as_int(dj)));
-              rank += static_cast<int>(dq == dj) & static_cast<int>(q < jo);
-            });
-          }
-          if (!unlimited || p.ragged) {  // a finite neighborDist / absent slots: count who is a neighbour
-            cnt = 0;
-            for_n<8>(GN, [&](const int q) {
-              cnt += static_cast<int>(__int_as_float(__builtin_amdgcn_ds_bpermute(gbase + 4 * q, __float_as_int(dj))) < INFINITY);
-            });
-          }
-          // (neighborDist = inf -- Config.SENSING_HORIZON, RVOPolicy.py:27 -- makes every other agent a neighbour)
-          const int n = cnt < p.rvo_max_neighbors ? cnt : p.rvo_max_neighbors;
-          if (valid) {
-            if (jo == 0) sh_nb[ag] = n;
-            if (dj < INFINITY && rank < n) {
-              // (the ego's own collaboration coefficient where the caller drew one per agent: RVOPolicy.py:77-90)
-              const float cf = k.s.rvo_collab ? k.s.rvo_collab[env0 * N + ag] : collab;
-              Lmat[rank * CS + ag] = half_plane_sel(mpos, f2(sh_fvx[ag], sh_fvy[ag]), sh_frad[ag],
-                                                     f2(sh_fpx[eb + j], sh_fpy[eb + j]), f2(sh_fvx[eb + j], sh_fvy[eb + j]),
-                                                     sh_frad[eb + j], cf, inv_h, inv_dt);
-            }
+        }
+        if (!unlimited || p.ragged) {  // a finite neighborDist / absent slots: count who is a neighbour
+          cnt = 0;
+          for_n<8>(GN, [&](const int q) {
+            cnt += static_cast<int>(__int_as_float(__builtin_amdgcn_ds_bpermute(gbase + 4 * q, __float_as_int(dj))) < INFINITY);
+          });
+        }
+        // (neighborDist = inf -- Config.SENSING_HORIZON, RVOPolicy.py:27 -- makes every other agent a neighbour)
+        const int n = cnt < p.rvo_max_neighbors ? cnt : p.rvo_max_neighbors;
+        if (valid) {
+          if (jo == 0) sh_nb[ag] = n;
+          if (dj < INFINITY && rank < n) {
+            // (the ego's own collaboration coefficient where the caller drew one per agent: RVOPolicy.py:77-90)
+            const float cf = k.s.rvo_collab ? k.s.rvo_collab[env0 * N + ag] : collab;
+            Lmat[rank * CS + ag] = half_plane_sel(mpos, f2(sh_fvx[ag], sh_fvy[ag]), sh_frad[ag],
+                                                   f2(sh_fpx[eb + j], sh_fpy[eb + j]), f2(sh_fvx[eb + j], sh_fvy[eb + j]),
+                                                   sh_frad[eb + j], cf, inv_h, inv_dt);
           }
         }
-        if (wave0 && rvo) {  // the preferred velocity (float64 sqrt + divide), while the other waves finish the pairs
-          const double vx = r.gx - r.px, vy = r.gy - r.py;
-          const double sc = divd(r.ps, sqrtd(vx * vx + vy * vy));  // RVOPolicy.py:66-67
-          sh_fprx[lane] = static_cast<float>(sc * vx);
-          sh_fpry[lane] = static_cast<float>(sc * vy);
-          sh_fms[lane] = static_cast<float>(r.ps);
+      }
+      if (wave0 && rvo) {  // the preferred velocity (float64 sqrt + divide), while the other waves finish the pairs
+        const double vx = r.gx - r.px, vy = r.gy - r.py;
+        const double sc = divd(r.ps, sqrtd(vx * vx + vy * vy));  // RVOPolicy.py:66-67
+        sh_fprx[lane] = static_cast<float>(sc * vx);
+        sh_fpry[lane] = static_cast<float>(sc * vy);
+        sh_fms[lane] = static_cast<float>(r.ps);
+      }
+      WG_SYNC();
+      if (N > G16) {
+        // ================= more than 16 agents per env: one WAVE per querying agent solves the whole programme
+        // cooperatively (lane j = line j): linearProgram2 as "first violated line" ballots with the 1-D programme of that
+        // line solved by the lanes holding the lines before it, then linearProgram3 if it ends infeasible
+        // (cagpu_grouplp.inc; bit-identical to the sequential algorithm).  Solving EVERY line's 1-D programme in advance,
+        // as below, is N^3 / 2 intersections per env -- at N = 50 that and its scan took 37 k of the step's 138 k cycles,
+        // for 1.3 .. 3 programmes a query really needs.
+        const int wq = tid >> 6, jl = tid & 63;
+        for (int c = wq; c < n_live; c += NT / 64) {  // wave-uniform
+          const int ag = sh_q[c];
+          const int nf = sh_nb[ag];
+          const float4 ln = Lmat[((jl < nf) ? jl : 0) * CS + ag];
+          F2 v;
+          const int f2_ = lp2_group<64>(jl < nf, f2(ln.x, ln.y), f2(ln.z, ln.w), sh_fms[ag], f2(sh_fprx[ag], sh_fpry[ag]), false,
+                                        v, jl, jl);
+          if (f2_ != NOFAIL) lp3_group<64>(nf, f2_, f2(ln.x, ln.y), f2(ln.z, ln.w), sh_fms[ag], v, jl, jl);
+          if (jl == 0) { sh_vrx[ag] = v.x; sh_vry[ag] = v.y; }
         }
         WG_SYNC();
-        TICK(2);
-        if (N > G16 && !EXP(32)) {
-          // ================= more than 16 agents per env: one WAVE per querying agent solves the whole programme
-          // cooperatively (lane j = line j): linearProgram2 as "first violated line" ballots with the 1-D programme of that
-          // line solved by the lanes holding the lines before it, then linearProgram3 if it ends infeasible
-          // (cagpu_grouplp.inc; bit-identical to the sequential algorithm).  Solving EVERY line's 1-D programme in advance,
-          // as below, is N^3 / 2 intersections per env -- at N = 50 that and its scan took 37 k of the step's 138 k cycles,
-          // for 1.3 .. 3 programmes a query really needs.
-          const int wq = tid >> 6, jl = tid & 63;
-          for (int c = wq; c < n_live; c += NT / 64) {  // wave-uniform
-            const int ag = sh_q[c];
-            const int nf = sh_nb[ag];
-            const float4 ln = Lmat[((jl < nf) ? jl : 0) * CS + ag];
-            F2 v;
-            const int f2_ = lp2_group<64>(jl < nf, f2(ln.x, ln.y), f2(ln.z, ln.w), sh_fms[ag], f2(sh_fprx[ag], sh_fpry[ag]), false,
-                                          v, jl, jl);
-            if (f2_ != NOFAIL) lp3_group<64>(nf, f2_, f2(ln.x, ln.y), f2(ln.z, ln.w), sh_fms[ag], v, jl, jl);
-            if (jl == 0) { sh_vrx[ag] = v.x; sh_vry[ag] = v.y; }
-          }
-          WG_SYNC();
-          TICK(12);
-          if (wave0 && rvo) v_orca = f2(sh_vrx[lane], sh_vry[lane]);
-          if (wave0) PRIO(3, 0, 3, 3, 3, 3, 3, 3); else PRIO(1, 0, 2, 0, 0, 0, 0, 1);
-        } else {
+        if (wave0 && rvo) v_orca = f2(sh_vrx[lane], sh_vry[lane]);
+        if (wave0) PRIO(3); else PRIO(0);
+      } else {
         // ================= P2b: linearProgram1 of EVERY line i against the lines before it, one thread per (agent, i).
         // The 1-D optimum on line i depends on the lines [0, i), the speed disc and the preferred velocity only -- not
         // on the running result of linearProgram2 -- so all of them are computed side by side (min / max are exact and
@@ -1088,24 +1022,16 @@ __global__ __launch_bounds__(NT, MULTI ? (NC == 20 ? 2 : 4) : 1) void ca_kernel(
         // loop over the lines m < i runs to a wave-uniform bound instead of N - 2 for everybody.
         const int n_lp1 = n_live * (N - 1);
         const float inv_live = 1.0f / static_cast<float>(n_live > 0 ? n_live : 1);
-                for (int base_ = 0; base_ < n_lp1; base_ += NT) {
+        for (int base_ = 0; base_ < n_lp1; base_ += NT) {
           const int w = base_ + tid;
           const bool item = w < n_lp1;
-          int i_hi, i, ag;
-          if (!EXP(32)) {
-            // highest lines first: a second round (more than NT / (N - 1) queries in the tile) holds the lines with the
-            // FEWEST predecessors, i.e. the cheap ones
-            const int w_lo = base_ + (tid & ~63);  // the wave's first item holds its highest line
-            i_hi = __builtin_amdgcn_readfirstlane((N - 2) - static_cast<int>((static_cast<float>(w_lo) + 0.5f) * inv_live));
-            const int wq = item ? static_cast<int>((static_cast<float>(w) + 0.5f) * inv_live) : 0;
-            i = item ? (N - 2) - wq : 0;
-            ag = sh_q[item ? w - wq * n_live : 0];
-          } else {
-            const int w_hi = (base_ + (tid | 63) < n_lp1) ? base_ + (tid | 63) : n_lp1 - 1;  // the wave's last item
-            i_hi = __builtin_amdgcn_readfirstlane(static_cast<int>((static_cast<float>(w_hi) + 0.5f) * inv_live));
-            i = item ? static_cast<int>((static_cast<float>(w) + 0.5f) * inv_live) : 0;
-            ag = sh_q[item ? w - i * n_live : 0];
-          }
+          // highest lines first: a second round (more than NT / (N - 1) queries in the tile) holds the lines with the
+          // FEWEST predecessors, i.e. the cheap ones
+          const int w_lo = base_ + (tid & ~63);  // the wave's first item holds its highest line
+          const int i_hi = __builtin_amdgcn_readfirstlane((N - 2) - static_cast<int>((static_cast<float>(w_lo) + 0.5f) * inv_live));
+          const int wq = item ? static_cast<int>((static_cast<float>(w) + 0.5f) * inv_live) : 0;
+          const int i = item ? (N - 2) - wq : 0;
+          const int ag = sh_q[item ? w - wq * n_live : 0];
           const bool live = item && i < sh_nb[ag];
           const float4 li = Lmat[i * CS + ag];
           const F2 Pi = f2(li.x, li.y), Di = f2(li.z, li.w);
@@ -1147,11 +1073,10 @@ LP1_UNROLL
           }
         }
         WG_SYNC();
-        TICK(12);
         // ================= linearProgram2 = a scan over the lines, one lane per agent (agent wave); infeasible
         // programmes (4.6 % of the queries at N = 10) are queued for the cooperative linearProgram3 pass
         int failf = NOFAIL;
-        if (wave0) PRIO(3, 0, 3, 3, 3, 3, 3, 3);
+        if (wave0) PRIO(3);
         if (wave0 && rvo) {
           const int n = sh_nb[lane];
           const float radius = sh_fms[lane];
@@ -1180,19 +1105,12 @@ LP1_UNROLL
           }
         }
         WG_SYNC();
-        TICK(15);
         // ================= linearProgram3 for the queued agents.  N <= 10 (at most 9 lines): one WAVE per agent, all pair
         // intersections of the embedded linearProgram2 in one step (lp3_wave8); otherwise one 16-lane group per agent
         // while N <= 16 (lane j = half-plane j; ballot + DPP row reductions), the whole wave beyond (cagpu_grouplp.inc)
         const int n3 = sh_q3[0];
-#ifdef CAGPU_WGTIME
-        if (tid == 0) {
-          wg_info = static_cast<unsigned long long>(n3) | (static_cast<unsigned long long>(sh_q3[ROW + 1]) << 8);
-          wg_lp3 = wall_clock64();
-        }
-#endif
-        if (n3 > 0 && !AB(2) && !EXP(8)) {  // workgroup-uniform (EXP(8): experiment, results invalid)
-          PRIO(3, 3, 3, 2, 3, 3, 3, 3);
+        if (n3 > 0) {  // workgroup-uniform
+          PRIO(3);
           auto solve3 = [&](auto gs_tag) {
             constexpr int GS = decltype(gs_tag)::value;
             constexpr int GROUPS = NT / GS;
@@ -1213,15 +1131,7 @@ LP1_UNROLL
             for (int q3 = wv; q3 < n3; q3 += NT / 64) {
               const int ent = sh_q3[1 + q3], agf = ent & 0xFF, ff = (ent >> 8) & 0xFF;  // (bits 16 ..: the line count)
               F2 v = f2(sh_vrx[agf], sh_vry[agf]);
-#ifdef CAGPU_WGTIME
-              int it3 = 0;
-              TICK(13);  // (slot 13: barrier + queue / entry loads; slot 14: lp3_wave8 itself, wave 0's entries only)
-              lp3_wave8(Lmat + agf, CS, (ent >> 16) & 0xFF, ff, sh_fms[agf], v, tid & 63, &it3);
-              TICK(14);
-              if (tid == 0) wg_info += static_cast<unsigned long long>(it3) << 24;
-#else
               lp3_wave8(Lmat + agf, CS, (ent >> 16) & 0xFF, ff, sh_fms[agf], v, tid & 63);
-#endif
               if ((tid & 63) == 0) { sh_vrx[agf] = v.x; sh_vry[agf] = v.y; }
             }
           } else if (N <= G16) {
@@ -1231,16 +1141,10 @@ LP1_UNROLL
           }
           WG_SYNC();
           if (failf != NOFAIL) v_orca = f2(sh_vrx[lane], sh_vry[lane]);
-          if (wave0) PRIO(3, 0, 3, 3, 3, 3, 3, 3); else PRIO(1, 0, 2, 0, 0, 0, 0, 1);
-        }
+          if (wave0) PRIO(3); else PRIO(0);
         }
       }
-#ifdef CAGPU_WGTIME
-      if (tid == 0) wg_lp3 = wall_clock64() - wg_lp3;  // the linearProgram3 pass (incl. its barrier), 10 ns ticks
-#endif
-      TICK(3);
       // ================= A2c: policy post-processing (env.py:305-323) and move (agent.py:192-241), one lane per agent
-      TICK(0);
       if (wave0) {
         double spd = 0.0, dh = 0.0;
         if (query) {
@@ -1260,7 +1164,6 @@ LP1_UNROLL
             ext_policy_action(pol, k.ext[2 * i], k.ext[2 * i + 1], r.ps, p.max_heading_change, spd, dh);
           }
         }
-        TICK(4);
         const float a0f = static_cast<float>(spd), a1f = static_cast<float>(dh);  // float32 `all_actions`
         if (active && k.o.actions) reinterpret_cast<float2*>(k.o.actions)[i + ring_a] = make_float2(a0f, a1f);
         if (active && k.o.orca_vel)  // parity hook: the velocity rvo2 chose for this agent (RVOPolicy.py:93), 0 if not queried
@@ -1278,7 +1181,6 @@ LP1_UNROLL
         }
       }
       do_sense = active;
-      TICK(5);
     }
 
     // ================= sensing passes: once, and a second time for envs that auto-reset in this step
@@ -1289,7 +1191,7 @@ LP1_UNROLL
       if (wave0) {
         sh_px[lane] = r.px; sh_py[lane] = r.py; sh_vx[lane] = r.vx; sh_vy[lane] = r.vy; sh_rad[lane] = r.rad;
         if (do_sense) {
-          if (AB(16)) { eg.dist = r.px; eg.prx = 1.0; eg.pry = 0.0; eg.heading_ego = r.heading; } else eg = ego_frame(r.px, r.py, r.gx, r.gy, r.heading);
+          eg = ego_frame(r.px, r.py, r.gx, r.gy, r.heading);
           sh_prx[lane] = eg.prx;
           sh_pry[lane] = eg.pry;
         }
@@ -1297,11 +1199,10 @@ LP1_UNROLL
         if (RO) sh_q[lane] = 0;  // reused below: case index + 1 of an env that auto-resets in this step
       }
       WG_SYNC();
-      TICK(6);
 
       // ---- P3: every (agent, other) pair: centre distance -> collision gap, sensor key, p_orth
       //      (env.py:458-512; OtherAgentsStatesSensor.py:76-107)
-      PRIO(1, 0, 2, 1, 1, 2, 1, 1);
+      PRIO(1);
       if (NC != 0 && p.sort_mode != CA_SORT_TIME_TO_IMPACT) {
         // N compiled in: one item per UNORDERED pair {a, b} -- the float64 square root, the collision gap and the
         // horizon test are the same for both directions; only d - r_host - r_other (operand order) and p_orth (the
@@ -1309,10 +1210,8 @@ LP1_UNROLL
         // the N/2 antipodal pairs, then N self entries: N (N + 1) / 2 items, 220 per 4-env tile = ONE round of 256.
         constexpr int NN = NC ? NC : 2, HALF = (NN - 1) / 2, PE = NN * (NN + 1) / 2;
         const int n_un = tile_envs * PE;
-        DUP(2048)
 #pragma unroll
         FOR_ITEMS_UPTO(w, n_un) {
-          if (AB(32)) continue;
           const int le2 = div_small<PE>(w, 1.0f / static_cast<float>(PE));
           const int u = w - __mul24(le2, PE), eb = __mul24(le2, NN);
           if (!sh_sense[eb]) continue;  // sensing is decided per env
@@ -1361,10 +1260,8 @@ LP1_UNROLL
           gmat[a1 * CS + gb] = both ? d - (br + ar) : INFINITY;
         }
       } else {
-      DUP(2048)
 #pragma unroll
       FOR_PAIR_ITEMS(w) {
-        if (AB(32)) continue;
         const int ag = div_small<NC>(w, inv_n);
         const int j = w - __mul24(ag, N);
         if (!sh_sense[ag]) continue;
@@ -1396,13 +1293,10 @@ LP1_UNROLL
       }
       WG_SYNC();
 
-      TICK(7);
       // ---- P4: rank the candidates of every agent and emit its rows (OtherAgentsStatesSensor.py:20-55,109-143)
-      PRIO(1, 0, 1, 1, 0, 1, 0, 1);
-      DUP(4096)
+      PRIO(0);
 #pragma unroll
       FOR_PAIR_ITEMS(w) {
-        if (AB(64)) continue;
         const int ag = div_small<NC>(w, inv_n);
         const int j = w - __mul24(ag, N);
         if (!sh_sense[ag]) continue;
@@ -1506,7 +1400,7 @@ LP1_UNROLL
       }
       // ---- A3 (wave 0, while the other waves finish the pair items of P4): rewards + collision flag (env.py:394-456),
       // observation scalars
-      if (wave0) PRIO(3, 0, 3, 3, 3, 3, 3, 3);
+      if (wave0) PRIO(3);
       // a map set (the single-step kernel and the n-step form's MSET instantiations; workgroup-uniform test): the env's
       // grid, its index read by the env's agent 0 lane and handed to the others -- the wall tests of this step see the map
       // the env had when the step began (in an n-step launch: what the same lane stored at the last step's auto-reset)
@@ -1558,12 +1452,10 @@ LP1_UNROLL
         }
       }
 
-      TICK(8);
       // No workgroup barrier here: A4 reads what A3 wrote (flags, episode scratch), and both run on the agent wave --
       // a wave-level fence is enough, and A4 overlaps with the other waves' second round of P4 instead of following it.
       if (wave0) wave_sync();
 
-      TICK(9);
       // ---- A4 (wave 0): done / game over (env.py:514-553), auto-reset (vec_env.py:120-128), episode statistics
       bool need_second = false;
       if (k.mode == MODE_STEP && pass == 0) {
@@ -1625,10 +1517,6 @@ LP1_UNROLL
         }
       }
       const int again = __syncthreads_or(need_second ? 1 : 0);
-#ifdef CAGPU_WGTIME
-      if (tid == 0 && again) wg_info |= 1ull << 16;
-#endif
-      TICK(10);
       // final record (CaFinal; workgroup-uniform tests): the terminal rows of the envs that reset, from where P4 / A3 left
       // them (LDS when staged, else read back from the output rows: every wave's stores to them are drained first)
       float* fin_tile = nullptr;
@@ -1659,7 +1547,7 @@ LP1_UNROLL
       }
       if (RO || !again) {
         // ---- the tile's observation block leaves LDS as one contiguous, coalesced copy
-        if (STAGE && !AB(128)) {
+        if (STAGE) {
           const long total = tile_cnt * W;
           float* dst = obs_tile;
           if (k.mode == MODE_RESET && k.reset_mask) {
@@ -1694,8 +1582,7 @@ LP1_UNROLL
     } else if (sense_pass(0)) {
       sense_pass(1);
     }
-    if (MULTI || EXP(4)) WG_SYNC();  // the union is free again before the next step's ORCA view (n-step kernel only)
-    TICK(11);
+    if (MULTI) WG_SYNC();  // the union is free again before the next step's ORCA view (n-step kernel only)
   };
   if (MULTI) {
     const int n_steps = (k.mode == MODE_STEP) ? k.n_steps : 1;
@@ -1711,15 +1598,6 @@ LP1_UNROLL
     one_step();
   }
 
-#ifdef CAGPU_ABLATE
-  __syncthreads();
-  if (tid < 16) atomicAdd(&g_prof[tid], sh_prof[tid]);
-  if (tid < 16 && blockIdx.x < 1024) g_wgprof[blockIdx.x * 16 + tid] = sh_prof[tid];
-#endif
-#ifdef CAGPU_WGTIME
-  unsigned long long wg_t1 = 0;
-  if (tid == 0) wg_t1 = wall_clock64();
-#endif
   // ---- store my agent.  The pointers are re-read from the kernarg segment here (laundered so the compiler does
   // not keep 19 pointer pairs alive in SGPRs across the whole kernel).
   if (active && k.mode != MODE_OBSERVE && (k.mode == MODE_STEP || !k.reset_mask || k.reset_mask[e])) {
@@ -1747,18 +1625,6 @@ LP1_UNROLL
   //  epoch-tagged device-scope atomic per tile for its range + one arrival ticket -- so that cagpu_ga3c could skip its packing
   //  launch (6.9 us of a 143 us config-3 step).  1 366 tiles x 2 same-address atomics cost ~43 ns each, serialised: the step
   //  kernel went 34 -> 129 us (config 3: 146 -> 241 us per step, same box).  compact_kernel does the same with 80 workgroups.)
-#ifdef CAGPU_WGTIME
-  if (tid == 0 && blockIdx.x < 4096) {
-    unsigned hw = 0, xcc = 0;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    unsigned long long* o = g_wgtime + blockIdx.x * 8;
-    o[0] = wg_t0; o[1] = wg_t1; o[2] = wall_clock64(); o[3] = wg_info; o[4] = hw; o[5] = xcc; o[6] = wg_lp3;
-    o[7] = clock64() - wg_c0;  // shader-clock cycles over the workgroup's life (against o[2] - o[0] at 100 MHz: the clock)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) g_wgphase[blockIdx.x * 16 + q] = wg_ph[q];
-  }
-#endif
 }
 
 #include "cagpu_pipe.inc"
@@ -1839,8 +1705,7 @@ int check_params(const CaParams* p, const CaState* s, const CaOut* o) {
 }
 
 // ---- launch plan.  Everything that selects a kernel instantiation or a tile geometry is decided here from the
-// arguments and the device's CU count alone (no environment variables in the product build: -DCAGPU_KNOBS adds the
-// experiment knobs of scratch/, parsed once; -DCAGPU_ABLATE also the in-kernel phase timers).
+// arguments and the device's CU count alone (no environment variables).
 thread_local char g_last_kernel[160] = "";
 
 int device_cus() {  // CU count of the current device, cached per device id
@@ -1853,28 +1718,6 @@ int device_cus() {  // CU count of the current device, cached per device id
     cache[dev].store(c, std::memory_order_relaxed);
   }
   return c;
-}
-
-struct Knobs {  // experiment overrides (-DCAGPU_ABLATE builds only); -1 / 0 = not set
-  int tile = 0, nt = 0, stage = -1, no_nc = 0, rollout_fused = 0;
-};
-const Knobs& knobs() {
-#if defined(CAGPU_ABLATE) || defined(CAGPU_KNOBS)
-  static const Knobs kn = [] {
-    Knobs q;
-    if (const char* e = std::getenv("CAGPU_TILE")) q.tile = std::atoi(e);
-    if (const char* e = std::getenv("CAGPU_NT")) q.nt = std::atoi(e);
-    if (std::getenv("CAGPU_STAGE")) q.stage = 1;
-    if (std::getenv("CAGPU_NOSTAGE")) q.stage = 0;
-    if (std::getenv("CAGPU_NO_NC")) q.no_nc = 1;
-    if (std::getenv("CAGPU_ROLLOUT_FUSED")) q.rollout_fused = 1;
-    return q;
-  }();
-  return kn;
-#else
-  static const Knobs kn;
-  return kn;
-#endif
 }
 
 // n single-step launches in place of one n-step launch: the next launch writes the next slot of the caller's output ring
@@ -1947,20 +1790,14 @@ int launch_main3(const KArgs& k, size_t total, hipStream_t st) {
 template <int NT, bool STAGE>
 int launch_main2(const KArgs& k, size_t total, hipStream_t st) {
   if constexpr (NT <= 256) {  // the 512-thread geometry exists for large N only
-    if (k.p.num_agents == 10 && !knobs().no_nc) {  // N and the tile size compiled in
+    if (k.p.num_agents == 10) {  // N and the tile size compiled in
       if (k.tile_envs == ROW / 10) return launch_main3<NT, STAGE, 10>(k, total, st);
       if (k.tile_envs == 4) return launch_main3<NT, STAGE, 10, 4>(k, total, st);
     }
-#ifndef CAGPU_FAST
-    if (k.p.num_agents == 20 && k.tile_envs == ROW / 20 && !knobs().no_nc)  // BASELINE config 3 (4096 x 20)
+    if (k.p.num_agents == 20 && k.tile_envs == ROW / 20)  // BASELINE config 3 (4096 x 20)
       return launch_main3<NT, STAGE, 20>(k, total, st);
-#endif
   }
-#ifdef CAGPU_FAST  // scratch builds: only the N = 10 instantiations are compiled
-  return fail(CA_EUNSUPPORTED, "cagpu: CAGPU_FAST experiment build supports num_agents == 10 only%s");
-#else
   return launch_main3<NT, STAGE, 0>(k, total, st);
-#endif
 }
 
 template <int NT>
@@ -1981,12 +1818,8 @@ int launch_main(const KArgs& k, hipStream_t st) {
   // the unstaged layout, so the staged layout is only kept up to three per CU)
   const long per_cu = static_cast<long>((160 * 1024) / total);
   const long resident_staged = (per_cu < 3 ? per_cu : 3) * n_cu;
-  bool crowded = wgs > resident_staged;
-  if (knobs().stage == 1) crowded = false;
-#ifdef CAGPU_FAST
-  crowded = true;
-#endif
-  if (total > 64 * 1024 || crowded || knobs().stage == 0) {  // give up the staging area
+  const bool crowded = wgs > resident_staged;
+  if (total > 64 * 1024 || crowded) {  // give up the staging area
     un_sense = lds_sense_bytes(N, W, 0, tti, cs);
     stage = false;
     total = lds_fixed_bytes() + (un_orca > un_sense ? un_orca : un_sense);
@@ -1998,25 +1831,17 @@ int launch_main(const KArgs& k, hipStream_t st) {
   const long lds_cap = static_cast<long>((160 * 1024) / total);
   const long reg_cap = (N == 20) ? 2 : 4;  // (ca_kernel's __launch_bounds__)
   const long fused_resident = (lds_cap < reg_cap ? lds_cap : reg_cap) * n_cu;
-  if (k.mode == MODE_STEP && k.n_steps > 1 && wgs > fused_resident && !knobs().rollout_fused) {
+  if (k.mode == MODE_STEP && k.n_steps > 1 && wgs > fused_resident) {
     KArgs k1 = k;
     k1.n_steps = 1;
     for (int i = 0; i < k.n_steps; ++i) {
-#ifdef CAGPU_FAST
-      const int rc = launch_main2<256, false>(k1, total, st);
-#else
       const int rc = stage ? launch_main2<256, true>(k1, total, st) : launch_main2<256, false>(k1, total, st);
-#endif
       if (rc) return rc;
       ring_advance(k1);
     }
     return CA_OK;
   }
-#ifdef CAGPU_FAST
-  return launch_main2<NT, false>(k, total, st);
-#else
   return stage ? launch_main2<NT, true>(k, total, st) : launch_main2<NT, false>(k, total, st);
-#endif
 }
 
 // The software-pipelined kernel (cagpu_pipe.inc): the caller handed over CaState.next_action, the agent count has an
@@ -2026,9 +1851,6 @@ bool pipe_eligible(const KArgs& k) {
   const int n = k.p.num_agents;
   if (!k.s.next_action || k.stage_obs) return false;
   if (k.s.rvo_collab || k.s.rvo_heading_noise || k.s.ext_state) return false;  // (per-step inputs belong to the step that consumes them)
-#ifdef CAGPU_FAST
-  if (n != 10) return false;
-#endif
   if (!(n == 10 || n == 8 || n == 6 || n == 5 || n == 4 || n == 3 || n == 2)) return false;  // (the instantiations)
   if (k.mode != MODE_STEP && k.mode != pipe::MODE_PLAN) return false;
   if (k.p.sort_mode != CA_SORT_CLOSEST_FIRST) return false;
@@ -2047,9 +1869,9 @@ uint32_t next_pack_epoch() {
   return epoch_source.fetch_add(1, std::memory_order_relaxed);
 }
 
-#ifndef CAGPU_PIPE_YIELD_T
-#define CAGPU_PIPE_YIELD_T 2   // (A/B builds: 0 = off)
-#endif
+// KArgs.yield_t of a launch that gets the progress-fair priorities: the lead, in steps, over its CU's slowest workgroup from
+// which a workgroup yields (the mechanism and its measurements: PIPE_PRIO in cagpu_pipe.inc)
+constexpr int PIPE_YIELD_T = 2;
 template <int NC, int TE, bool MULTI>
 int launch_pipe2(const KArgs& k0, hipStream_t st) {
   using G = pipe::Geo<NC, TE>;
@@ -2061,10 +1883,10 @@ int launch_pipe2(const KArgs& k0, hipStream_t st) {
   k.inv_dt_f = 1.0f / static_cast<float>(k.p.rvo_dt);
   // progress-fair priorities (PIPE_PRIO): an n-step launch whose workgroups are all resident at once and share their CUs
   k.yield_t = 0;
-  if (MULTI && CAGPU_PIPE_YIELD_T > 0) {
+  if (MULTI) {
     const long cus = device_cus();
     const long per_cu = (160 * 1024) / static_cast<long>(G::LDS) < 4 ? (160 * 1024) / static_cast<long>(G::LDS) : 4;
-    if (grid > cus && grid <= per_cu * cus) k.yield_t = CAGPU_PIPE_YIELD_T;
+    if (grid > cus && grid <= per_cu * cus) k.yield_t = PIPE_YIELD_T;
   }
   std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_pipe_kernel<%d, %d, %s> grid=%u lds=%zu mode=%d%s%s%s%s", NC, TE,
                 MULTI ? "true" : "false", grid, static_cast<size_t>(G::LDS), k.mode, k.yield_t > 0 ? " fair" : "",
@@ -2124,14 +1946,12 @@ int launch_pipe(const KArgs& k, hipStream_t st) {
     // one launch per step 11.78 -> 11.92 / 12.18: below the 0.5 us bar in every mode a caller sees; not built
     // (profiles/r06_kernel_geometry.md).
     case 10: return launch_pipe1<10, 4>(k, st);
-#ifndef CAGPU_FAST
     case 8: return launch_pipe1<8, 8>(k, st);
     case 6: return launch_pipe1<6, 10>(k, st);
     case 5: return launch_pipe1<5, 12>(k, st);
     case 4: return launch_pipe1<4, 16>(k, st);
     case 3: return launch_pipe1<3, 21>(k, st);
     case 2: return launch_pipe1<2, 32>(k, st);
-#endif
     default: return fail(CA_EUNSUPPORTED, "cagpu: no pipelined instantiation for this agent count%s");
   }
 }
@@ -2183,30 +2003,19 @@ int launch_any(const KArgs& k0, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   KArgs k = k0;
   const int N = k.p.num_agents;
-#ifndef CAGPU_NOPIPE
   if (pipe_eligible(k)) return launch_pipe(k, st);
-#endif
   if (k.mode != pipe::MODE_PLAN && N > 64) return launch_big(k, st);
   if (k.mode == pipe::MODE_PLAN) return fail(CA_EUNSUPPORTED, "cagpu_plan: needs CaState.next_action, num_agents in {2, 3, 4, 5, 6, 8, 10}, closest_first sorting and a grid of at most 4 x CUs or at least 8 x CUs tiles%s");
   k.tile_envs = ROW / N;
-  k.col_stride = (N > 32) ? (CAGPU_CSPAD ? (N | 1) : N) : CS_ROW;  // single-env tiles: only the N columns in use (see ca_kernel)
+  k.col_stride = (N > 32) ? (N | 1) : CS_ROW;  // single-env tiles: only the N columns in use (see ca_kernel)
   // N = 10: tiles of 4 envs instead of 6 while that still gives at most 4 workgroups per CU (all co-resident, evenly
   // spread): 27.3 vs 30.9 us at 4096 envs, 23.3 vs 27.6 at 2048; beyond that the 6-env tile wins
   // (profiles/r01_kernel_geometry.md)
-  if (N == 10 && k.mode == MODE_STEP && !knobs().tile) {
-    if ((static_cast<long>(k.p.num_envs) + 3) / 4 <= 4L * device_cus()) k.tile_envs = 4;
-  }
-  if (knobs().tile >= 1 && knobs().tile < k.tile_envs) k.tile_envs = knobs().tile;
+  if (N == 10 && k.mode == MODE_STEP && (static_cast<long>(k.p.num_envs) + 3) / 4 <= 4L * device_cus()) k.tile_envs = 4;
   // N > 32: the tile is a single env whose N^2 pair items (and N wave-wide linear programs) keep 8 waves busy, and
   // its LDS footprint allows only one or two workgroups per CU anyway
-  int nt = (N > 32) ? 512 : 256;
-  if (knobs().nt) nt = knobs().nt;
-#ifdef CAGPU_FAST
+  if (N > 32) return launch_main<512>(k, st);
   return launch_main<256>(k, st);
-#else
-  if (nt <= 256) return launch_main<256>(k, st);
-  return launch_main<512>(k, st);
-#endif
 }
 
 int pick_block(int N) { return N <= 64 ? 64 : (N <= 128 ? 128 : 256); }
@@ -2410,19 +2219,12 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
     k.ring_env = p->num_envs;
     // the in-kernel snapshot is the pipelined n-step kernel's (launch_pipe with n_steps > 1): every other form of the call
     // leaves it to the caller (cagpu_ring_snapshots says which, from the same arguments)
-#ifdef CAGPU_NOPIPE   // (a build whose launcher never picks the pipelined kernel must not promise its snapshot either)
-    const bool can = false;
-#else
     const bool can = n_steps > 1 && pipe_eligible(k);
-#endif
     if (c.query_snapshot) return can ? 1 : 0;
     if (c.snapshot_delta != 0 && !can)
       return fail(CA_EUNSUPPORTED, "cagpu_rollout_ring: snapshot_delta needs the pipelined n-step kernel (cagpu_ring_snapshots() == 1 for these arguments)%s");
     k.snap_delta = c.snapshot_delta;
   }
-#ifdef CAGPU_ABLATE
-  if (const char* ab = std::getenv("CAGPU_ABLATE")) k.ablate = std::atoi(ab);
-#endif
   return launch_any(k, stream);
 }
 
@@ -2715,13 +2517,7 @@ int cagpu_render_maps(const CaParams* p, const CaState* s, const CaMapSet* set, 
 }
 
 namespace {
-constexpr size_t ga3c_lds_bytes() {
-#if defined(CAGPU_GA3C_SOLO)   // timing experiment (scratch/ga3c_phases.py): one workgroup per CU, a wave has its SIMD to itself
-  return 100 * 1024;
-#else
-  return ga3c::LDS_BYTES;
-#endif
-}
+constexpr size_t GA3C_LDS = ga3c::LDS_BYTES;
 int ga3c_check_net(const CaNet* net) {
   const void* w[] = {net->lstm_kernel, net->lstm_bias, net->layer1_kernel, net->layer1_bias, net->layer2_kernel,
                      net->layer2_bias, net->fc1_kernel, net->fc1_bias, net->logits_kernel, net->logits_bias,
@@ -2740,20 +2536,17 @@ int ga3c_launch_ext(ga3c::Args& k, const ga3c::Ext& ex, void* stream) {
   hipError_t e = hipSuccess;
   if (!lds_raised[dev_id & 15]) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ga3c::ga3c_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(ga3c_lds_bytes()));
+                            static_cast<int>(GA3C_LDS));
     if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: hipFuncSetAttribute: %s", hipGetErrorString(e));
     lds_raised[dev_id & 15] = true;
   }
   k.slots = 2 * device_cus();
   k.force_tile = 0;
-#if defined(CAGPU_KNOBS)
-  if (const char* ft = std::getenv("CAGPU_GA3C_TILE")) k.force_tile = std::atoi(ft);
-#endif
   const unsigned grid = static_cast<unsigned>((k.B + 31) / 32);  // (B < 2^31)
   std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ga3c_kernel<true> %s grid=%u lds=%zu rows=%ld width=%d%s%s%s",
-                ex.query ? "query" : "sim", grid, ga3c_lds_bytes(), k.B, k.W - 1, k.logits ? " logits" : "",
+                ex.query ? "query" : "sim", grid, GA3C_LDS, k.B, k.W - 1, k.logits ? " logits" : "",
                 ex.value ? " value" : "", ex.action ? " action" : "");
-  hipLaunchKernelGGL(ga3c::ga3c_kernel<true>, dim3(grid), dim3(ga3c::NT), ga3c_lds_bytes(), static_cast<hipStream_t>(stream), k, ex);
+  hipLaunchKernelGGL(ga3c::ga3c_kernel<true>, dim3(grid), dim3(ga3c::NT), GA3C_LDS, static_cast<hipStream_t>(stream), k, ex);
   e = hipGetLastError();
   if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
   return CA_OK;
@@ -2837,7 +2630,6 @@ int ga3c_impl(const CaParams* p, const CaState* s, const float* obs, const CaNet
                        net->net_index, epoch);
   }
   static_assert(ga3c::LDS_BYTES <= 80 * 1024, "two workgroups per CU");
-  constexpr size_t GA3C_LDS = ga3c_lds_bytes();
   if (val) {  // the value head rides on the other instantiation; the default launch below is untouched
     ga3c::Ext ex;
     std::memset(&ex, 0, sizeof(ex));
@@ -2856,9 +2648,6 @@ int ga3c_impl(const CaParams* p, const CaState* s, const float* obs, const CaNet
   }
   k.slots = 2 * device_cus();
   k.force_tile = 0;
-#if defined(CAGPU_KNOBS)
-  if (const char* ft = std::getenv("CAGPU_GA3C_TILE")) k.force_tile = std::atoi(ft);
-#endif
   // the tile height (64 / 48 / 32 rows) is chosen on the device from the number of live rows: the grid covers the worst
   // case (32-row tiles); workgroups beyond the last tile leave at once
   const unsigned grid = static_cast<unsigned>((k.B + 31) / 32);
@@ -3070,45 +2859,6 @@ int cagpu_observe(const CaParams* p, const CaState* s, const CaOut* o, void* str
   return launch_any(k, stream);
 }
 
-#ifdef CAGPU_STEPTIME
-int cagpu_debug_steptime(unsigned long long* out) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(pipe::g_steptime), sizeof(unsigned long long) * 1024 * 66);
-  return 0;
-}
-#endif
-#ifdef CAGPU_PIPETIME
-int cagpu_debug_pipetime(unsigned long long* out) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(pipe::g_pipetime), sizeof(unsigned long long) * 1024 * 32);
-  return 0;
-}
-#endif
-#ifdef CAGPU_WGTIME
-int cagpu_debug_wgtime(unsigned long long* out) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wgtime), sizeof(unsigned long long) * 4096 * 8);
-  return 0;
-}
-int cagpu_debug_wgphase(unsigned int* out) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wgphase), sizeof(unsigned int) * 4096 * 16);
-  return 0;
-}
-#endif
-#ifdef CAGPU_ABLATE
-int cagpu_debug_wgprof(unsigned long long* out) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wgprof), sizeof(unsigned long long) * 1024 * 16);
-  return 0;
-}
-int cagpu_debug_prof(unsigned long long* out, int reset) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)); }
-  return 0;
-}
-#endif
 
 uint64_t cagpu_ga3c_packed_bytes(void) { return static_cast<uint64_t>(ga3c::PK_TOTAL) * sizeof(ga3c::u32x4); }
 

@@ -23,14 +23,6 @@
 //     11 logits stay on the f32 MFMA.  The order of issue of the LSTM step and of layer2 / fc1 is placed by hand (below).
 namespace ga3c {
 
-#ifdef CAGPU_ABLATE
-#define GTICK(slot) do { if (tid == 0) { const unsigned long long n_ = clock64(); atomicAdd(&g_prof[slot], n_ - tp_); tp_ = n_; } } while (0)
-#define LTICK(k) do { if (wv_u == 0) { const unsigned long long n_ = clock64(); lseg[k] += n_ - lt_; lt_ = n_; } } while (0)
-#else
-#define GTICK(slot) do {} while (0)
-#define LTICK(k) do {} while (0)
-#endif
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -69,7 +61,7 @@ struct Args {
   float* logits;  // [B, 11] or nullptr
   const int32_t* rows;  // packed list of the rows to evaluate + their count at [B] (compact_kernel), or nullptr
   int slots;            // workgroups resident at once (2 per CU): the tile height is chosen against it
-  int force_tile;       // 0 = balanced per-tile heights, or 32 / 48 / 64 for every tile (tests)
+  int force_tile;       // 0 = balanced per-tile heights (what the launchers pass), or 32 / 48 / 64 for every tile
   // FUSED SENSING (obs == nullptr): the kernel computes each evaluated agent's ego-centric observation itself from the
   // simulator state -- OtherAgentsStatesSensor.sense + the observation assembly (OtherAgentsStatesSensor.py:58-144,
   // agent.py:323-327) for exactly the rows the network reads -- instead of fetching the row the step kernel stored
@@ -174,7 +166,7 @@ __global__ __launch_bounds__(CP_NT) void compact_kernel(const uint32_t* __restri
 
 // Rows per workgroup tile: 64, 48 or 32 (whole 16-row MFMA blocks), chosen PER TILE.  With the packed list the row count
 // is whatever is alive, and one height for the whole launch quantises coarsely: a round of resident tiles (512 slots = 2
-// workgroups per CU) costs 297 / 225 / 160 us for 64 / 48 / 32 rows (scratch/ga3c_tiles.py, 4096 x 20: a fixed part --
+// workgroups per CU) costs 297 / 225 / 160 us for 64 / 48 / 32 rows (one forced height per launch, 4096 x 20: a fixed part --
 // weights from L2, barriers -- plus ~4.3 us per row of the CU's two tiles), so 26 .. 32 k rows all cost one full round of
 // 64-row tiles (profiles/r04_ga3c_rows.json: 310 .. 317 us flat), although 26 k rows are 19 % less work.  Balanced plan:
 // the launch takes R = ceil(rows / (64 * slots)) rounds whatever the heights, so spread the rows' 16-row blocks EVENLY
@@ -187,7 +179,7 @@ struct Tile {
   long row0;  // its first row in the packed list
 };
 __device__ __forceinline__ Tile tile_of(const long n_rows, const int slots, const int force_tile, const long t) {
-  if (force_tile) return Tile{force_tile, t * force_tile};  // (tests, scratch/ga3c_tiles.py: one height for the launch)
+  if (force_tile) return Tile{force_tile, t * force_tile};  // (one height for the launch; the launchers pass 0)
   const long blocks = (n_rows + 15) >> 4;
   if (blocks == 0) return Tile{32, t * 32};  // nothing is alive: every workgroup leaves at once
   const long rounds = (blocks + 4L * slots - 1) / (4L * slots);
@@ -518,9 +510,6 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
   const Tile tile = tile_of(n_rows, g.slots, g.force_tile, blockIdx.x);
   const int tm = tile.tm, nrb = tm >> 4;  // rows / 16-row blocks of THIS tile
   const long row0 = tile.row0;
-#ifdef CAGPU_ABLATE
-  unsigned long long tp_ = clock64();
-#endif
 
   // ---- the tile's rows: slot t holds packed row rows[row0 + t] (or row row0 + t itself without the packed list)
   if (row0 >= n_rows) return;  // workgroup-uniform (the grid covers the worst case: every row alive, 32-row tiles)
@@ -698,9 +687,7 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
       const int co = (cc + 1 < g.W) ? cc : g.W - 2;  // W >= 6 (a query: W >= 2)
       xv[j] = orow[co];
     }
-    GTICK(14);  // (ablate builds: kernel start -> every load issued; GTICK(15): -> the barrier passed; GTICK(0): the rest)
     __syncthreads();  // h is zeroed, the table is written
-    GTICK(15);
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       const int c = c0 + j;
@@ -722,7 +709,6 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
     }
   }
 
-  GTICK(0);
   // ---- this wave's LSTM weights: gate g4 (i, j, f, o), units 16 wv .. 16 wv + 15 = packed column block 4 g4 + wv.
   // h part: two planes x two k-blocks per gate.  x part (rows 0..6 of the kernel) + bias: the float32 MFMA is NOT used --
   // measured (scratch/mfma_valu.hip, profiles/r05_mfma_valu.txt): v_mfma_f32_16x16x4_f32 blocks the SIMD's VALU for its 32
@@ -777,7 +763,6 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
   const float* const xb1 = xs + (((q == 1) ? 1 : 0) * TM + m) * 4;
   __syncthreads();
 
-  GTICK(1);
   // a lane's state: rows 16 rb + m, units 16 wv + 4 q + r
   float cst[4][4], hst[4][4];
   int seqr[4];
@@ -801,13 +786,6 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
   // cell update to carry.
   // ALL_LIVE: every real row of the tile has the tile's longest sequence (the usual case: every agent senses every other),
   // so no row ever keeps its state and the two selects per element go.
-#ifdef CAGPU_ABLATE
-  // wave 0's cycles in the segments of an LSTM step, summed over the steps: [0] MFMA stages, [1] the last row block's cell
-  // update, [2] wait at the first barrier, [3] split + store of h_t+1, [4] wait at the second barrier; -> g_prof[7 .. 11],
-  // g_prof[12] += steps, g_prof[13] += row blocks x steps
-  const int wv_u = __builtin_amdgcn_readfirstlane(wv);
-  unsigned long long lseg[5] = {0, 0, 0, 0, 0}, lt_ = clock64();
-#endif
   auto lstm_steps = [&](auto nrb_c, auto all_live_c) {
     constexpr int NRB = decltype(nrb_c)::value;
     constexpr bool ALL_LIVE = decltype(all_live_c)::value;
@@ -831,9 +809,6 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
       f32x4 acc[2][4];
       Gate gt;
       float xn0 = 0.f, xn1 = 0.f;
-#ifdef CAGPU_ABLATE
-      if (wv_u == 0) lt_ = clock64();
-#endif
       // stage s: the MFMAs of row block s (s < NRB) with the cell update of row block s - 1 (s >= 1) between them
 #pragma clang loop unroll(full)
       for (int s = 0; s <= NRB; ++s) {
@@ -879,16 +854,13 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
             GA3C_FENCE();
           }
         }
-        if (s == NRB) LTICK(0);
         if (s == NRB) {  // the last row block's cell update has no MFMAs to hide behind (the SIMD's other wave has)
 #pragma clang loop unroll(full)
           for (int u = 0; u < NG; ++u) gate_op<ALL_LIVE>((ALL_LIVE ? GATE_ORDER[u % GATE_OPS] : GATE_ORDER_SEL[u % GATE_OPS_SEL]), gt, acc[prv], cst[s - 1], hst[s - 1], live);
           GA3C_FENCE();
         }
       }
-      LTICK(1);
       __syncthreads();  // every wave has read h_t
-      LTICK(2);
 #pragma clang loop unroll(full)
       for (int rb = 0; rb < NRB; ++rb) {
         float* hw = hp + ((rb * 16 + m) * HP_LD + wv * 16 + 4 * q) / 2;  // units 16 wv + 4 q .. + 3 of row 16 rb + m
@@ -896,17 +868,8 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
         *reinterpret_cast<uint2*>(hw) = make_uint2(pk2(a0, a1), pk2(a2, a3));
         *reinterpret_cast<uint2*>(hw + HP_PLANE) = make_uint2(pk2(lo_part(a0), lo_part(a1)), pk2(lo_part(a2), lo_part(a3)));
       }
-      LTICK(3);
       __syncthreads();  // h_t+1 and the planes of x_t+1 are complete
-      LTICK(4);
     }
-#ifdef CAGPU_ABLATE
-    if (tid == 0) {
-      for (int k = 0; k < 5; ++k) atomicAdd(&g_prof[7 + k], lseg[k]);
-      atomicAdd(&g_prof[12], static_cast<unsigned long long>(tmax));
-      atomicAdd(&g_prof[13], static_cast<unsigned long long>(tmax * NRB));
-    }
-#endif
   };
   const bool all_live = misc[2] >= tmax;
   using std::integral_constant;
@@ -920,7 +883,6 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
     else lstm_steps(integral_constant<int, 2>{}, integral_constant<bool, false>{});
   }
 
-  GTICK(2);
   // ---- layer1_input = concat[host, h_final]: h_final = the planes the last step wrote (all zero without a step), the
   // four host inputs go through one exact f32 MFMA.  The activations take over the LSTM's LDS after the barrier.
   f32x4 acc[4][4];
@@ -948,7 +910,6 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
   __syncthreads();
   store_relu_t(act, g.net.layer1_bias, acc, m, q, wv, nrb, amax);  // layer1/BiasAdd, layer1/Relu
   __syncthreads();
-  GTICK(3);
   zero_acc();
   if (nrb == 4) dense_pipe<8, 4>(act, ACT_LD, pk + PK_L2, acc, lane, m, q, wv);
   else if (nrb == 3) dense_pipe<8, 3>(act, ACT_LD, pk + PK_L2, acc, lane, m, q, wv);
@@ -956,7 +917,6 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
   __syncthreads();
   store_relu_t(act, g.net.layer2_bias, acc, m, q, wv, nrb, amax);
   __syncthreads();
-  GTICK(4);
   zero_acc();
   if (nrb == 4) dense_pipe<8, 4>(act, ACT_LD, pk + PK_FC1, acc, lane, m, q, wv);
   else if (nrb == 3) dense_pipe<8, 3>(act, ACT_LD, pk + PK_FC1, acc, lane, m, q, wv);
@@ -965,7 +925,6 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
   store_relu_t(act, g.net.fc1_bias, acc, m, q, wv, nrb, amax_unused);
   __syncthreads();
 
-  GTICK(5);
   // ---- logits_p: 11 columns = one (padded) column block; wave w takes row block w.  EXT: column 11 of the block is
   // logits_v (the value head, `Squeeze` of the graph) on the same exact-f32 MFMA; the columns do not see each other.
   if (wv < nrb) {  // (wave-uniform)
@@ -1002,7 +961,6 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
 
   if (!(amax < 65504.f)) atomicOr(&g_fault, 2u);
   (void)amax_unused;
-  GTICK(6);
   // ---- argmax(Softmax) -> index into network.Actions (GA3CCADRLPolicy.py:81-83); ties -> first, like np.argmax
   if (tid < TM && need) {
     const long i = row_of(tid);

@@ -207,8 +207,7 @@ __device__ __forceinline__ void gminmax8(float& lo_of_his, float& hi_of_los) {
 
 // Lcol: the agent's half-planes in LDS (line j at Lcol[j * stride]); n <= 9 lines; `begin` = first failing line;
 // res: wave-uniform in / out; lane = 0 .. 63.
-__device__ void lp3_wave8(const float4* Lcol, int stride, int n, int begin, float radius, F2& res, int lane,
-                          int* iterations = nullptr) {
+__device__ void lp3_wave8(const float4* Lcol, int stride, int n, int begin, float radius, F2& res, int lane) {
   const int k = lane >> 3, m = lane & 7;
   // lane l < n keeps line l for the outer violation test; row k keeps line k for the projection
   const float4 ll = Lcol[((lane < n) ? lane : 0) * stride];
@@ -284,6 +283,5 @@ __device__ void lp3_wave8(const float4* Lcol, int stride, int n, int begin, floa
     if (!failed) res = r2;  // an infeasible embedded programme keeps the previous result (lp3)
     depth = detf(Di, Pi - res);
     cur = i + 1;
-    if (iterations) *iterations += 1;
   }
 }

@@ -49,22 +49,12 @@ enum { M_NEED = 0, M_NLIVE = 1, M_AGAIN = 2, M_CEGO = 3, M_CP3 = 4, M_CP2 = 5, M
        M_CLP3 = 9, M_CRC = 10, M_YIELD = 11, M_PSLOT = 12 };  // sh_misc slots (3 ..: arrival counters)
 enum { MODE_PLAN = 3 };                   // (continues MODE_STEP / MODE_RESET / MODE_OBSERVE)
 
-// -DCAGPU_PIPETIME (scratch/pipetime.py): wall-clock stamps (100 MHz) of the LAST step of a launch, one row per workgroup:
-// slots 0 .. 15 by wave 0, 16 .. 31 by wave 4 (each at its own stage boundaries); experiment builds only.
-//
 // The workgroup barrier of a step (B_P; B_A once at the start; the n-step loop's B_5 is a full __syncthreads()).  What the
 // waves exchange travels through LDS only, so the barrier waits for this wave's LDS traffic (lgkmcnt), not for the
 // acknowledgement of its outstanding global stores (vmcnt).  The one place where global stores of different waves to the
 // SAME address must stay ordered (the reset-observation copy over rows P4 and A3 wrote) drains vmcnt itself before it
-// signals.  -DCAGPU_PIPE_FULLBAR=1: __syncthreads() everywhere (A/B experiments).
-#ifndef CAGPU_PIPE_FULLBAR
-#define CAGPU_PIPE_FULLBAR 0
-#endif
-#if CAGPU_PIPE_FULLBAR
-#define PIPE_SYNC() __syncthreads()
-#else
+// signals.
 #define PIPE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#endif
 
 // Barriers among SOME of the workgroup's waves (gfx950 has no named barriers): an arrival counter in LDS.  sig() publishes
 // this wave's LDS writes and counts it in; wait_for() polls until `target` waves have arrived.  Every hand-over behind B_P
@@ -78,9 +68,6 @@ enum { MODE_PLAN = 3 };                   // (continues MODE_STEP / MODE_RESET /
 // AUDITS the arrival counters -- each must hold exactly its target.  A miscounted hand-over (an edit of the helper counts)
 // or a poll that ran out before its producer arrived leaves a counter off its target; bit 0 of the device's fault word is
 // raised, which the host reads with cagpu_device_faults() (core.BatchedSim.check_faults(), after every GPU test).
-#ifndef CAGPU_PIPE_AUDIT
-#define CAGPU_PIPE_AUDIT 1   // (A/B builds: 0 = no audit, as in round 3)
-#endif
 // (g_fault, the device's fault word, is defined in cagpu.hip: bit 0 is this file's, bit 1 the GA3C-CADRL range guard's)
 __device__ __forceinline__ void sig(int* c) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -88,13 +75,11 @@ __device__ __forceinline__ void sig(int* c) {
 }
 // SL: the s_sleep between two polls (x 64 cycles).  A poll is an LDS read + a v_readfirstlane: it takes a VALU issue slot from
 // the waves that work.  The hand-overs of a step's critical chain poll at SL = 1; a wave whose wait is NOT on that chain as a
-// rule (CAGPU_PIPE_NCSLEEP: the S-pair waves behind their P4, the O-pair waves behind their 1-D programmes) sleeps longer.
+// rule (NC_SLEEP: the S-pair waves behind their P4, the O-pair waves behind their 1-D programmes) sleeps longer.
 // Measured (r06g, same box; VALU instructions of a 50-step launch 211.9 M -> 208.3 M at 4, LDS instructions 30.2 M -> 27.8 M):
 // 2000-step rollout 7.73 -> 7.70 (2) / 7.70 (4) / 7.72 (8) us per step, ring of 50 9.03 -> 9.01 / 9.00 / 9.02; 1024 envs (one
 // workgroup per CU: the wake-up counts, the issue slots do not) 7.96 -> 7.96 / 7.97 / 8.04.  2 it is.
-#ifndef CAGPU_PIPE_NCSLEEP
-#define CAGPU_PIPE_NCSLEEP 2
-#endif
+constexpr int NC_SLEEP = 2;
 template <int SL = 1>
 __device__ __forceinline__ void wait_for(int* c, const int target) {
   for (int spin = 0; spin < (1 << 22); ++spin) {
@@ -117,30 +102,11 @@ __device__ __forceinline__ void wait_for2(int* c1, const int t1, int* c2, const 
 }
 
 // Wave priorities (s_setprio): wave 0's chains and the linearProgram3 / scan / post stages at 3 (everybody else of the
-// workgroup waits for them), the ORCA pair phases at 2; the sensing pair phases P3 / P4 at CAGPU_PIPE_SPRIO / _SPRIO4.
+// workgroup waits for them), the ORCA pair phases at 2; the sensing pair phases P3 / P4 at S_PRIO / S_PRIO4.
 // Measured in one gpurun call (profiles/r03_kernel_geometry.md): P3 / P4 at 1 / 0: 15.55 us per step; 0 / 0: 15.66; 1 / 1:
 // 15.66; 2 / 2: 16.4; 3 / 3: 16.8 -- the CU's VALU issue is nearly saturated now, and what the ORCA chain (the longer half)
 // does not get it cannot make up.
-#ifndef CAGPU_PIPE_SPRIO
-#define CAGPU_PIPE_SPRIO 1
-#endif
-#ifndef CAGPU_PIPE_SPRIO4
-#define CAGPU_PIPE_SPRIO4 0
-#endif
-#ifndef CAGPU_PIPE_OPRIO
-#define CAGPU_PIPE_OPRIO 2
-#endif
-// -DCAGPU_PIPE_DUP=<mask> (scratch/dup_pmc.sh): run an idempotent phase twice -- the difference of the launch's VALU / SALU / LDS
-// instruction counters is what the phase costs in situ.  1: P2, 2: P2b, 4: P3, 8: P4, 16: ego frame, 32: post
-#ifndef CAGPU_PIPE_DUP
-#define CAGPU_PIPE_DUP 0
-#endif
-// -DCAGPU_PIPE_STAGGER=<n> (experiment): the workgroups that share a CU start n x 1024 cycles apart (slot 0 .. 3 from a
-// per-CU counter keyed by the hardware's CU id): a launch starts with every workgroup of a CU in the same phase at the same
-// time -- they contend for the same pipes in lock step until their different workloads have pulled them apart
-#ifndef CAGPU_PIPE_STAGGER
-#define CAGPU_PIPE_STAGGER 0
-#endif
+constexpr int S_PRIO = 1, S_PRIO4 = 0, O_PRIO = 2;
 
 // Progress-fair issue priorities among the workgroups that share a CU (round 6; KArgs.yield_t = T > 0, set by the launcher for an
 // n-step launch whose whole grid is resident at once).  A short n-step launch ends with its slowest workgroup, and within a CU
@@ -150,49 +116,27 @@ __device__ __forceinline__ void wait_for2(int* c1, const int t1, int* c2, const 
 // publishes the number of steps it has completed in a per-CU table in global memory (row keyed by the hardware's CU id, slot
 // from a per-CU arrival counter) and reads its CU-mates' once per step -- on the first S-pair wave, at the end of its step,
 // where nobody waits for it --; a workgroup that is >= T steps ahead of the slowest one of its CU runs its next step with every
-// wave at priority <= CAGPU_PIPE_YLEVEL.  Only s_setprio operands depend on it: results cannot change.  Measured (same box,
+// wave at priority <= Y_LEVEL.  Only s_setprio operands depend on it: results cannot change.  Measured (same box,
 // 4096 x 10): spread of the workgroups' totals within a CU 11.4 -> 5.2 us, 20-step launch 10.23 -> 9.83 us per step, 50-step 9.36 ->
 // 9.02, 2000-step rollout 7.66 -> 7.73 (the exchange + yielding cost ~1 % where no tail is left to win).
-#ifndef CAGPU_PIPE_YLEVEL
-#define CAGPU_PIPE_YLEVEL 1
-#endif
+constexpr int Y_LEVEL = 1;
 __device__ unsigned int g_cu_slot[16 * 256];
 __device__ unsigned int g_prog[16 * 256 * 4];
 // FAIR is a template parameter of the kernel: the instantiation without it is round 5's code to the instruction (every PIPE_PRIO
 // a plain s_setprio) and serves every launch the launcher does not switch the mechanism on for -- grids that are not resident at
 // once, one workgroup per CU, single steps; the branches around the priorities alone cost 1.6 - 1.9 % there (r06f).
-#define PIPE_PRIO(x) do { if (FAIR && yield_) __builtin_amdgcn_s_setprio((x) < CAGPU_PIPE_YLEVEL ? (x) : CAGPU_PIPE_YLEVEL); else __builtin_amdgcn_s_setprio(x); } while (0)
+#define PIPE_PRIO(x) do { if (FAIR && yield_) __builtin_amdgcn_s_setprio((x) < Y_LEVEL ? (x) : Y_LEVEL); else __builtin_amdgcn_s_setprio(x); } while (0)
 // The yield flag of a step travels in bit 8 of the word every wave reads behind the publish barrier anyway (M_NLIVE: the tile's
 // planned agents, <= 64): no LDS read of its own on any wave's way out of the barrier.  The exchange writes M_YIELD before B_5,
 // wave 0 folds it into the next publish.
 #define PIPE_NLIVE(word) ((word) & 0xFF)
 #define PIPE_YIELD_OF(word) (FAIR && ((word) >> 8) != 0)
-#define PIPE_DUP(bit, var) for (int dup_ = 0; dup_ < ((CAGPU_PIPE_DUP & (bit)) ? 2 : 1); ++dup_, ({ asm volatile("" : "+v"(var)); }))
-
-// -DCAGPU_STEPTIME (scratch/steptime.py): wall-clock stamps (100 MHz) of wave 0 at the START of the launch and at the end of
-// EVERY step (up to 63) of the n-step kernel, one row per workgroup + the CU it ran on: is a workgroup persistently slow, or are
-// the first steps of every launch slow?
-#ifdef CAGPU_STEPTIME
-__device__ unsigned long long g_steptime[1024 * 66];
-#define ST(slot) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024 && (slot) < 64) g_steptime[blockIdx.x * 66 + (slot)] = wall_clock64(); } while (0)
-#else
-#define ST(slot) do {} while (0)
-#endif
-#ifdef CAGPU_PIPETIME
-__device__ unsigned long long g_pipetime[1024 * 32];
-#define PT(slot) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) g_pipetime[blockIdx.x * 32 + (slot)] = wall_clock64(); } while (0)
-#define PTV(slot, v) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) g_pipetime[blockIdx.x * 32 + (slot)] = (v); } while (0)
-// (sh_misc[14] / [15]: sum / maximum of the lines linearProgram3 acted on, per tile)
-#define PIPE_LP3_ITERS_DECL int lp3_it_ = 0
-#define PIPE_LP3_ITERS_ARG , &lp3_it_
-#define PIPE_LP3_ITERS_NOTE do { if ((threadIdx.x & 63) == 0) { atomicAdd(&sh_misc[14], lp3_it_); atomicMax(&sh_misc[15], lp3_it_); } } while (0)
-#else
-#define PT(slot) do {} while (0)
-#define PTV(slot, v) do {} while (0)
-#define PIPE_LP3_ITERS_DECL do {} while (0)
-#define PIPE_LP3_ITERS_ARG
-#define PIPE_LP3_ITERS_NOTE do {} while (0)
-#endif
+// PIPE_ONCE(var) <phase>: the phase as the body of a loop of ONE trip that ends by handing `var` through an empty asm (a VGPR
+// in, the same VGPR out: no instruction).  What is left of a switch that could run a phase twice for counter measurements; the
+// switch is gone, the shape stays because the compiler's output rests on it: the one-trip loop changes how the loops inside
+// the phase are strength-reduced, the empty asm where `var` lives.  Without it all 112 instantiations of the kernel come out
+// as other code (other scalar registers, other instruction counts), and that is a change to measure, not to slip into a clean-up.
+#define PIPE_ONCE(var) for (int once_ = 0; once_ < 1; ++once_, ({ asm volatile("" : "+v"(var)); }))
 
 // floor(w / n) for the item decomposition of the 1-D programmes (w < 1200 items, n <= 64 planned agents) as (w * kMagic20.v[n]) >> 20:
 // exact on that range (checked exhaustively), two integer instructions per item and one scalar table load per wave and step
@@ -433,20 +377,10 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
     int ebase = active ? le * N : 0;
     // (global indices are written as (uniform array + tile base)[lane]: no 64-bit per-lane index to keep alive)
     float* obs_tile = k.o.obs + tile_base * W;
-    ST(0);
-#ifdef CAGPU_STEPTIME
-    if (tid == 0 && blockIdx.x < 1024) {
-      unsigned hw, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      g_steptime[blockIdx.x * 66 + 64] = ((xcc & 0xFull) << 16) | (hw & 0xFFFFull);
-    }
-#endif
     long out_base = tile_base, out_env = env0;  // n-step kernel: + this step's slot of the caller's output ring (cagpu_rollout_ring)
     // trajectory tape (TRAJ): this tile's rows / its envs' episode entries in the slot of the current step (uniform pointers)
     double* traj_tile = TRAJ ? k.traj_rows + tile_base * 12 : nullptr;
     int32_t* traj_ep = (TRAJ && k.traj_ep) ? k.traj_ep + env0 : nullptr;
-    PT(0);
     double px = 0.0, py = 0.0, vx = 0.0, vy = 0.0, heading = 0.0;
     float act0 = 0.f, act1 = 0.f;
     uint32_t flags = CA_DONE | CA_AT_GOAL;
@@ -596,20 +530,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
       if (!pre) { sh_vx[lane] = vx; sh_vy[lane] = vy; }
     };
 
-#if CAGPU_PIPE_STAGGER
-    if (!plan_mode && (CAGPU_PIPE_STAGGER > 0 ? MULTI : true)) {
-      unsigned hw, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      unsigned slot = 0;
-      if (lane == 0) slot = atomicAdd(&g_cu_slot[((xcc & 0xF) << 8) | ((hw >> 8) & 0xFF)], 1u);
-      slot = __builtin_amdgcn_readfirstlane(slot) & 3u;
-      for (unsigned q = 0; q < slot * (CAGPU_PIPE_STAGGER > 0 ? CAGPU_PIPE_STAGGER : -CAGPU_PIPE_STAGGER); ++q) __builtin_amdgcn_s_sleep(16);
-    }
-#endif
-    PT(1);
     PIPE_SYNC();  // B_A: `need`
-    PT(2);
     int step = 0;
     for (;;) {
       if (MULTI) {  // hide the loop invariance of everything derived from the thread id (see the O programme)
@@ -704,12 +625,9 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
           }
         }
       }
-      PT(3);
       publish(false);
-      PT(4);
       PIPE_SYNC();  // B_P
-      PT(5);
-      PIPE_DUP(16, px)
+      PIPE_ONCE(px)
       {  // the ego frame (agent.py:329-349, Dynamics.py:24-41) is the S half's business: the O half is already in P2
         const Ego eg = ego_frame(px, py, sh_gx[lane], sh_gy[lane], heading);
         sh_prx[lane] = eg.prx;
@@ -760,7 +678,6 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         wall_bits = active ? set_grid(k.map.static_bits, k.map_words, k.num_maps, m, a == 0) : nullptr;
       }
       wait_for(&sh_misc[M_CP3], 3);  // P3 done (the three S-pair waves)
-      PT(6);
       // ================= A3: rewards + collision flag (env.py:394-456), observation scalars
       if (active) {
         double nearest = INFINITY;
@@ -803,8 +720,6 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         row[4] = here ? static_cast<float>(sh_ps[lane]) : 0.f;
         row[5] = static_cast<float>(rad);
       }
-      PT(7);
-      PT(8);
       // ================= A4: done / game over (env.py:514-553), auto-reset (vec_env.py:120-128), episode statistics
       bool lost_plan = false;
       {
@@ -889,16 +804,8 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         if (rm != 0ull) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         need = need_next;
       }
-      PT(9);
       sig(&sh_misc[M_CA4]);  // done / auto-reset are decided: M_NEED, M_AGAIN, sh_rc, sh_flag (S-pair's reset copy, O's post)
-      PT(10);
-      PT(11);
       ++step;
-#ifdef CAGPU_STEPTIME
-      if (tid == 0 && blockIdx.x < 1024 && step < 64)   // (+ what the tile held in this step: planned agents, linearProgram3 queue)
-        g_steptime[blockIdx.x * 66 + step] = (wall_clock64() & 0xFFFFFFFFFFFFull) | (static_cast<unsigned long long>(PIPE_NLIVE(sh_misc[M_NLIVE])) << 48) |
-                                             (static_cast<unsigned long long>(sh_q3[0] & 0xFF) << 56);
-#endif
       plan_ok = !lost_plan;
       if (step >= n_steps) break;
       // The n-step loop carries NOTHING per lane in registers across its back edge: the post-move tile is in LDS anyway
@@ -962,7 +869,6 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         if (a == 0) { (ka->s.episode_step + env0)[le] = ep_step; (ka->s.reset_count + env0)[le] = reset_cnt; }
       }
     }
-    PT(12);
   } else if (role < 4) {
     // =====================================================================================================================
     // waves 1 - 3: the S-pair programme
@@ -971,7 +877,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
     // agents of this tile that exist (the last tile of a batch may hold fewer than TE envs): nothing is stored for the rest
     const int tile_cnt = (static_cast<long>(p.num_envs) * N - tile_base < TILE_N)
                              ? static_cast<int>(static_cast<long>(p.num_envs) * N - tile_base) : TILE_N;
-    __builtin_amdgcn_s_setprio(CAGPU_PIPE_SPRIO);
+    __builtin_amdgcn_s_setprio(S_PRIO);
     PIPE_SYNC();  // B_A
     if (FAIR && tid == 64) {  // my slot in my CU's row of the progress table (read back every step: nothing carried in registers)
       unsigned hw, xcc;
@@ -995,7 +901,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
       PIPE_SYNC();  // B_P
       const int nl_word = __builtin_amdgcn_readfirstlane(sh_misc[M_NLIVE]);
       const bool yield_ = PIPE_YIELD_OF(nl_word);
-      if (FAIR) PIPE_PRIO(CAGPU_PIPE_SPRIO);
+      if (FAIR) PIPE_PRIO(S_PRIO);
       // (FAIR: the CU-mates' progress words, fetched here -- a device-scope load, ~2 us under load -- and looked at at the end
       // of the step)
       unsigned prog_seen = 0;
@@ -1007,16 +913,16 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         const int n_live = PIPE_NLIVE(nl_word);
         const int hw = __builtin_amdgcn_readfirstlane(ts >> 6);
         if (n_live > P2_APR && hw < P2_HELPERS) {
-          PIPE_PRIO(CAGPU_PIPE_OPRIO);  // (the O half waits for these half-planes)
+          PIPE_PRIO(O_PRIO);  // (the O half waits for these half-planes)
           const float range_sq = sqf(static_cast<float>(p.sensing_horizon));
           int wl = ts & 63;
-          PIPE_DUP(1, wl)
+          PIPE_ONCE(wl)
           // (1 / time horizon, 1 / rvo_dt: the correctly rounded float quotients, divided once on the host -- KArgs.inv_h_f /
           // inv_dt_f -- instead of two IEEE divisions per helper wave and step)
           p2_round(0, 4 + hw, wl, n_live, !(range_sq < INFINITY), range_sq, p.rvo_max_neighbors,
                    static_cast<float>(p.rvo_collab_coeff), k.inv_h_f, k.inv_dt_f);
           sig(&sh_misc[M_CP2]);
-          PIPE_PRIO(CAGPU_PIPE_SPRIO);
+          PIPE_PRIO(S_PRIO);
         }
       }
       wait_for(&sh_misc[M_CEGO], 1);  // wave 0's ego frames
@@ -1028,7 +934,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         constexpr int HALF = (N - 1) / 2, PE = N * (N - 1) / 2;
         constexpr int n_un = TE * PE;
         int ts2 = ts;
-        PIPE_DUP(4, ts2)
+        PIPE_ONCE(ts2)
 #pragma unroll
         for (int base_ = 0; base_ < n_un; base_ += S_PAIR) {
           const int w = base_ + ts2;
@@ -1083,21 +989,21 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         const int n_live = PIPE_NLIVE(nl_word);
         const int hw = __builtin_amdgcn_readfirstlane(ts >> 6);
         if (n_live * (N - 1) > O_LANES && hw < P2_HELPERS) {
-          PIPE_PRIO(CAGPU_PIPE_OPRIO);
+          PIPE_PRIO(O_PRIO);
           wait_for(&sh_misc[M_CP2], 4 + ((n_live > P2_APR) ? P2_HELPERS : 0));  // every half-plane, the preferred velocities
           p2b_round(O_LANES, (hw << 6) + (ts & 63), n_live, kMagic20.v[n_live]);
           sig(&sh_misc[M_CP2B]);
-          PIPE_PRIO(CAGPU_PIPE_SPRIO);
+          PIPE_PRIO(S_PRIO);
         }
       }
       wait_for(&sh_misc[M_CP3], 3);
       // ================= P4: rank the candidates of every agent and emit its rows (OtherAgentsStatesSensor.py:20-55,
       // 109-143): one item per (agent, other), N - 1 lanes per agent
-      PIPE_PRIO(CAGPU_PIPE_SPRIO4);
+      PIPE_PRIO(S_PRIO4);
       {
         constexpr int n_p4 = TILE_N * GN;
         int ts2 = ts;
-        PIPE_DUP(8, ts2)
+        PIPE_ONCE(ts2)
 #pragma unroll
         for (int base_ = 0; base_ < n_p4; base_ += S_PAIR) {
           const int w = base_ + ts2;
@@ -1156,8 +1062,8 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
           o7[6] = d2mat[j * CS + ag];
         }
       }
-      PIPE_PRIO(CAGPU_PIPE_SPRIO);
-      wait_for<CAGPU_PIPE_NCSLEEP>(&sh_misc[M_CA4], 1);  // wave 0's A4: who is done, which envs reset
+      PIPE_PRIO(S_PRIO);
+      wait_for<NC_SLEEP>(&sh_misc[M_CA4], 1);  // wave 0's A4: who is done, which envs reset
       need = sh_misc[M_NEED] != 0;
       if (sh_misc[M_AGAIN]) {
         // ---- the observation of a freshly reset env is a pure function of its fixture case: computed once (cagpu_reset
@@ -1189,7 +1095,7 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
       }
       // linearProgram3: the four O waves solve queue entries 0 - 3 (+ 7 k); these three waves, idle by now, take entries
       // 4 - 6 (+ 7 k), so that a tile with up to seven infeasible agents (the slowest tiles of a launch) needs ONE round
-      wait_for<CAGPU_PIPE_NCSLEEP>(&sh_misc[M_CSCAN], 1);  // the O half's scan: the queue is complete
+      wait_for<NC_SLEEP>(&sh_misc[M_CSCAN], 1);  // the O half's scan: the queue is complete
       const int n3s = sh_q3[0];
       if (n3s > 4) {
         PIPE_PRIO(3);
@@ -1197,13 +1103,11 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         for (int q3 = 4 + wv; q3 < n3s; q3 += 7) {
           const int ent = sh_q3[1 + q3], agf = ent & 0xFF, ff = (ent >> 8) & 0xFF;
           F2 v = f2(sh_vrx[agf], sh_vry[agf]);
-          PIPE_LP3_ITERS_DECL;
-          lp3_wave8(Lmat + agf, CS, (ent >> 16) & 0xFF, ff, sh_fms[agf], v, ts & 63 PIPE_LP3_ITERS_ARG);
+          lp3_wave8(Lmat + agf, CS, (ent >> 16) & 0xFF, ff, sh_fms[agf], v, ts & 63);
           if ((ts & 63) == 0) { sh_vrx[agf] = v.x; sh_vry[agf] = v.y; }
-          PIPE_LP3_ITERS_NOTE;
           sig(&sh_misc[M_CLP3]);
         }
-        PIPE_PRIO(CAGPU_PIPE_SPRIO);
+        PIPE_PRIO(S_PRIO);
       }
       if (FAIR && ts < 64) {  // the progress exchange with the CU's other workgroups (see PIPE_PRIO above)
         const unsigned ps = static_cast<unsigned>(sh_misc[M_PSLOT]);
@@ -1222,7 +1126,6 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
           __hip_atomic_store(&g_prog[ps], (seq << 16) | ((mine + 1u) & 0xFFFFu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
-#if CAGPU_PIPE_AUDIT
       if (ts < 64) {  // the audit of the arrival counters (see sig() / wait_for()), on a wave nobody waits for any more:
         // behind the scan's signal every counter but M_CLP3 (whose only waiter, wave 4, polls it right now) and M_CRC
         // (this wave's own) is final and must hold exactly its target
@@ -1234,7 +1137,6 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         const bool off = ts < 16 && want >= 0 && sh_misc[slot] != want;
         if (__ballot(off) != 0ull && ts == 0) atomicOr(&g_fault, 1u);
       }
-#endif
       ++step;
       if (step >= n_steps) break;
       if (MULTI) obs_tile += k.ring_obs;  // (the next step's slot of the caller's output ring; 0 without one)
@@ -1264,23 +1166,22 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
       const int lane = to & 63;  // (agent index on wave 4)
       const int nl_word = __builtin_amdgcn_readfirstlane(sh_misc[M_NLIVE]);
       const bool yield_ = !pre && PIPE_YIELD_OF(nl_word);
-      if (w4) PIPE_PRIO(3); else PIPE_PRIO(CAGPU_PIPE_OPRIO);
+      if (w4) PIPE_PRIO(3); else PIPE_PRIO(O_PRIO);
       // ================= P2: every (planned agent, other) pair: neighbour rank (ascending distSq, ties by index:
       // Agent::insertAgentNeighbor) + ORCA half-plane.  A wave holds WHOLE agents, lane = (agent, one of its N - 1 others).
       const int n_live = PIPE_NLIVE(nl_word);
       const unsigned magic = kMagic20.v[n_live];   // (a scalar load, issued here, first used in P2b)
       const bool isq = w4 && sh_isq[lane] != 0;
-      if (w4) PT(16);
       // (steady state, more planned agents than the four O waves hold in one round: two S-pair waves take the next two
       // waves' worth beside them -- see the S-pair programme; 83 % of a launch's last-finishing tiles had a second round)
       const int helpers = (!pre && n_live > P2_APR) ? P2_HELPERS : 0;
       {
         const int wv = to >> 6;
         int wl = to & 63;
-        PIPE_DUP(1, wl) {
-        p2_round(0, wv, wl, n_live, unlimited, range_sq, p.rvo_max_neighbors, collab, inv_h, inv_dt);
-        for (int c0 = (4 + helpers) * P2_APW; c0 < n_live; c0 += P2_APR)  // uniform
-          p2_round(c0, wv, wl, n_live, unlimited, range_sq, p.rvo_max_neighbors, collab, inv_h, inv_dt);
+        PIPE_ONCE(wl) {
+          p2_round(0, wv, wl, n_live, unlimited, range_sq, p.rvo_max_neighbors, collab, inv_h, inv_dt);
+          for (int c0 = (4 + helpers) * P2_APW; c0 < n_live; c0 += P2_APR)  // uniform
+            p2_round(c0, wv, wl, n_live, unlimited, range_sq, p.rvo_max_neighbors, collab, inv_h, inv_dt);
         }
         if (isq) {  // the preferred velocity (float64 sqrt + divide), while the other waves finish the pairs
           const double vx = sh_gx[lane] - sh_px[lane], vy = sh_gy[lane] - sh_py[lane];
@@ -1299,25 +1200,21 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
           sh_vry[lane] = res0.y;
         }
       }
-      if (w4) PT(17);
       sig(&sh_misc[M_CP2]);
       wait_for(&sh_misc[M_CP2], 4 + helpers);  // the half-planes of all four O waves (and the helpers)
-      if (w4) PT(18);
       // ================= P2b: every line's 1-D programme (p2b_round above).  Steady state, more items than one round of the
       // four O waves holds (256 of up to 360): the next two waves' worth goes to the S-pair helpers (between their P3 and P4)
       const int n_lp1 = n_live * (N - 1);
       const int helpers_b = (!pre && n_lp1 > O_LANES) ? P2_HELPERS : 0;
       {
         int to2 = to;
-        PIPE_DUP(2, to2) {
+        PIPE_ONCE(to2) {
           p2b_round(0, to2, n_live, magic);
           for (int base_ = O_LANES + 64 * helpers_b; base_ < n_lp1; base_ += O_LANES) p2b_round(base_, to2, n_live, magic);  // uniform
         }
       }
-      if (w4) PT(19);
       sig(&sh_misc[M_CP2B]);
       if (w4) wait_for(&sh_misc[M_CP2B], 4 + helpers_b);  // every line's 1-D programme (the scan runs on wave 4 alone)
-      if (w4) PT(20);
       // ================= linearProgram2 = a scan over the lines, one lane per agent (wave 4); infeasible programmes are
       // queued for linearProgram3
       int failf = NOFAIL;
@@ -1344,10 +1241,8 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
           sh_q3[1 + atomicAdd(&sh_q3[0], 1)] = lane | (failf << 8) | (n << 16);
         }
       }
-      if (w4) PT(21);
       if (w4) sig(&sh_misc[M_CSCAN]);
-      else wait_for<CAGPU_PIPE_NCSLEEP>(&sh_misc[M_CSCAN], 1);  // the linearProgram3 queue is complete (wave 4 wrote it itself)
-      if (w4) PT(22);
+      else wait_for<NC_SLEEP>(&sh_misc[M_CSCAN], 1);  // the linearProgram3 queue is complete (wave 4 wrote it itself)
       const int n3 = sh_q3[0];
       // ================= linearProgram3 for the queued agents: one WAVE per agent (lp3_wave8, cagpu_grouplp.inc)
       if (n3 > 0) {
@@ -1358,28 +1253,21 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         for (int q3 = wv; q3 < n3; q3 += (pre ? 4 : 7)) {
           const int ent = sh_q3[1 + q3], agf = ent & 0xFF, ff = (ent >> 8) & 0xFF;  // (bits 16 ..: the line count)
           F2 v = f2(sh_vrx[agf], sh_vry[agf]);
-          PIPE_LP3_ITERS_DECL;
-          lp3_wave8(Lmat + agf, CS, (ent >> 16) & 0xFF, ff, sh_fms[agf], v, to & 63 PIPE_LP3_ITERS_ARG);
+          lp3_wave8(Lmat + agf, CS, (ent >> 16) & 0xFF, ff, sh_fms[agf], v, to & 63);
           if ((to & 63) == 0) { sh_vrx[agf] = v.x; sh_vry[agf] = v.y; }
-          PIPE_LP3_ITERS_NOTE;
           sig(&sh_misc[M_CLP3]);
         }
-        if (w4) PT(23);
       }
       // every queue entry is solved (wave 4 only: by these waves and the S-pair waves), and what wave 0's A4 decided in the
       // meantime (steady state only): envs that auto-reset, tiles that lost their plan -- polled together
       if (w4) wait_for2(&sh_misc[M_CLP3], n3, &sh_misc[M_CA4], pre ? 0 : 1);
-      else wait_for2<CAGPU_PIPE_NCSLEEP>(&sh_misc[M_CLP3], 0, &sh_misc[M_CA4], pre ? 0 : 1);
+      else wait_for2<NC_SLEEP>(&sh_misc[M_CLP3], 0, &sh_misc[M_CA4], pre ? 0 : 1);
       if (n3 > 0 && failf != NOFAIL) v_orca = f2(sh_vrx[lane], sh_vry[lane]);
       const bool need_next = !pre && sh_misc[M_NEED] != 0;
-      if (w4) PT(24);
-      if (w4) PTV(13, static_cast<unsigned long long>(n3) | (static_cast<unsigned long long>(PIPE_NLIVE(sh_misc[M_NLIVE])) << 8) |
-                          (static_cast<unsigned long long>(sh_misc[M_AGAIN]) << 16) |
-                          (static_cast<unsigned long long>(sh_misc[14]) << 24) | (static_cast<unsigned long long>(sh_misc[15]) << 32));
       // ================= post: Agent::update + RVOPolicy.py:96-111 -> the float32 action pair of the next step
       if (w4) {
         float4 pl = make_float4(0.f, 0.f, 0.f, 0.f);
-        PIPE_DUP(32, v_orca.x)
+        PIPE_ONCE(v_orca.x)
         if (isq) {
           // (rvo_action of cagpu_rules.inc, in this kernel's own text: the call changes its instructions)
           const float tsf = static_cast<float>(p.rvo_dt);
@@ -1405,7 +1293,6 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
         sh_plan[lane] = pl;
         // (an env that lost its plan -- auto-reset without reset_plan -- stores a stale row: wave 0 clears CA_PLAN_VALID)
         if (last && active) (reinterpret_cast<float4*>(k.s.next_action) + tile_base)[lane] = pl;
-        PT(25);
       }
       return need_next;
     };

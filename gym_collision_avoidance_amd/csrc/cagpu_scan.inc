@@ -64,10 +64,7 @@ __device__ bool hits_wall(const MapT& m, double x, double y, double radius) {
 }
 
 constexpr int SCAN_NT = 512;
-#ifndef CAGPU_SCAN_U
-#define CAGPU_SCAN_U 4
-#endif
-constexpr int SCAN_U = CAGPU_SCAN_U;  // samples per iteration of the march (see scan_kernel)
+constexpr int SCAN_U = 4;  // samples per iteration of the march (see scan_kernel)
 constexpr int SCAN_PAD = 8;  // cells of empty border around the LDS bitmap (beams are clipped to the grid box + ~1 cell)
 constexpr int HIST_AG = 4;   // agents whose range indices are staged before their history rows are rolled (scan_kernel)
 

@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""scratch/n20.py -- step time at 4096 envs x N RVO agents (N from env, default 20); with the knobs build CAGPU_NO_NC=1 selects
-the generic instantiation instead of the compile-time-N one"""
+"""scratch/n20.py -- step time at 4096 envs x N RVO agents (N from env, default 20) and the kernel that ran"""
 import numpy as np, torch, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gym_collision_avoidance_amd import _native as nat, core
