@@ -96,3 +96,30 @@ class Laser4(_Eval):        # static map + LaserScanSensor (config 5 in miniatur
         self.STATES_IN_OBS = ['is_learning', 'num_other_agents', 'dist_to_goal', 'heading_ego_frame', 'pref_speed',
                               'radius', 'other_agents_states', 'laserscan']
         _Eval.__init__(self)
+
+
+class StepRule(Config):     # the threshold scenes of tests/step_rule_scenes.py (oracle/gen_step_rule_golden.py): every constant
+    """a step rule reads comes from the JSON object in STEP_RULE_CONFIG: n, max_obs, sort, over ("all" / "agent0" /
+    "learning" = EVALUATE_MODE / TRAIN_SINGLE_AGENT / neither), and any of reward_time_step, getting_close_range,
+    reward_wiggly, wiggly_threshold, reward_collision_wall, sensing_horizon, use_map"""
+
+    def __init__(self):
+        import json
+        c = json.loads(os.environ["STEP_RULE_CONFIG"])
+        self.MAX_NUM_AGENTS_IN_ENVIRONMENT = c["n"]
+        self.MAX_NUM_OTHER_AGENTS_OBSERVED = c["max_obs"]
+        self.USE_STATIC_MAP = bool(c.get("use_map", False))
+        Config.__init__(self)
+        self.EVALUATE_MODE = c["over"] == "all"
+        self.TRAIN_SINGLE_AGENT = c["over"] == "agent0"
+        self.TRAIN_MODE = False
+        self.DT = 0.1
+        self.MAX_TIME_RATIO = 8.
+        self.STORE_HISTORY = False
+        self.AGENT_SORTING_METHOD = c["sort"]
+        self.REWARD_TIME_STEP = c.get("reward_time_step", 0.0)
+        self.GETTING_CLOSE_RANGE = c.get("getting_close_range", 0.2)
+        self.REWARD_WIGGLY_BEHAVIOR = c.get("reward_wiggly", 0.0)
+        self.WIGGLY_BEHAVIOR_THRESHOLD = c.get("wiggly_threshold", float("inf"))
+        self.REWARD_COLLISION_WITH_WALL = c.get("reward_collision_wall", -0.25)
+        self.SENSING_HORIZON = c.get("sensing_horizon", float("inf"))
