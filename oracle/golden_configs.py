@@ -101,7 +101,7 @@ class Laser4(_Eval):        # static map + LaserScanSensor (config 5 in miniatur
 class StepRule(Config):     # the threshold scenes of tests/step_rule_scenes.py (oracle/gen_step_rule_golden.py): every constant
     """a step rule reads comes from the JSON object in STEP_RULE_CONFIG: n, max_obs, sort, over ("all" / "agent0" /
     "learning" = EVALUATE_MODE / TRAIN_SINGLE_AGENT / neither), and any of reward_time_step, getting_close_range,
-    reward_wiggly, wiggly_threshold, reward_collision_wall, sensing_horizon, use_map"""
+    reward_wiggly, wiggly_threshold, reward_collision_wall, sensing_horizon, use_map, dt (oracle/gen_move_golden.py)"""
 
     def __init__(self):
         import json
@@ -113,7 +113,7 @@ class StepRule(Config):     # the threshold scenes of tests/step_rule_scenes.py 
         self.EVALUATE_MODE = c["over"] == "all"
         self.TRAIN_SINGLE_AGENT = c["over"] == "agent0"
         self.TRAIN_MODE = False
-        self.DT = 0.1
+        self.DT = c.get("dt", 0.1)
         self.MAX_TIME_RATIO = 8.
         self.STORE_HISTORY = False
         self.AGENT_SORTING_METHOD = c["sort"]

@@ -6,9 +6,7 @@ benchmark); the oracle is re-seeded from the GPU's bits every step.  Bars as eve
 
 Also here: the demonstration that the free-running divergence of the exact-swap fixture cases is caused by the libm bits
 alone (test_swap_cases_agree_on_the_gpus_libm_bits)."""
-import math
 import os
-import struct
 import sys
 
 import numpy as np
@@ -21,6 +19,7 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from tests import golden_util as gu  # noqa: E402
+from tests.device_libm import GpuLibm as _GpuLibm, step_resolved  # noqa: E402
 from tests.test_gpu_parity import F64, MASK, TOL, _mods, _swap_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -302,48 +301,6 @@ def test_config5_4096x50_map_laserscan_vs_oracle():
 
 
 # ---------------------------------------------------------------- the swap cases, on the GPU's own libm bits
-class _GpuLibm(object):
-    """atan2 / (sin, cos) tables filled by cagpu_debug_libm: the oracle's libm hooks look their operands up here; an
-    operand not seen yet is noted (and answered with the host's libm) so that the caller can evaluate it on the device and
-    repeat the step"""
-
-    def __init__(self):
-        self.at, self.sc, self.miss_at, self.miss_sc = {}, {}, [], []
-
-    @staticmethod
-    def _key(*v):     # by BITS: 0.0 == -0.0 as dict keys, but atan2(+0, -1) = pi and atan2(-0, -1) = -pi
-        return struct.pack("%dd" % len(v), *v)
-
-    def atan2(self, y, x):
-        v = self.at.get(self._key(y, x))
-        if v is None:
-            self.miss_at.append((y, x))
-            return math.atan2(y, x)
-        return v
-
-    def sincos(self, a):
-        v = self.sc.get(self._key(a))
-        if v is None:
-            self.miss_sc.append(a)
-            return math.sin(a), math.cos(a)
-        return v
-
-    def resolve(self):
-        """evaluate the noted operands on the device; -> number resolved"""
-        nat, core, orc = _mods()
-        n = len(self.miss_at) + len(self.miss_sc)
-        if self.miss_at:
-            m = np.array(self.miss_at, np.float64)
-            r, _ = nat.debug_libm(0, m[:, 0], m[:, 1])
-            self.at.update({self._key(*k): float(v) for k, v in zip(self.miss_at, r)})
-        if self.miss_sc:
-            m = np.array(self.miss_sc, np.float64)
-            s, c = nat.debug_libm(1, m)
-            self.sc.update({self._key(k): (float(a), float(b)) for k, a, b in zip(self.miss_sc, s, c)})
-        self.miss_at, self.miss_sc = [], []
-        return n
-
-
 def test_swap_cases_agree_on_the_gpus_libm_bits():
     """VERDICT r03 weak-1.  The ten-agent fixture cases in which two agents exchange places exactly meet head-on in a
     perfectly symmetric configuration; ORCA amplifies lateral round-off ~12x per step there, so a free-running GPU episode
@@ -382,15 +339,7 @@ def test_swap_cases_agree_on_the_gpus_libm_bits():
             worst, first_bad = 0.0, None
             for t in range(T):
                 if libm is not None:
-                    keep = {k: v.copy() for k, v in o.s.items()}
-                    for _ in range(8):    # policy atan2 -> heading sincos -> ego-frame atan2: three dependent batches
-                        o.step()
-                        if not libm.resolve():
-                            break
-                        for k, v in keep.items():
-                            o.s[k][:] = v
-                    else:
-                        raise AssertionError("libm table did not converge")
+                    step_resolved(o, libm)
                 else:
                     o.step()
                 for n in ("pos_x", "pos_y", "vel_x", "vel_y", "heading"):
