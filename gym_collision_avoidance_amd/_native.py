@@ -152,7 +152,7 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_step_log", "cagpu_rollout_log", "cagpu_step_ex", "cagpu_step_draw", "cagpu_policy_draw",
            "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes", "cagpu_ga3c_query", "cagpu_ga3c_value",
            "cagpu_generate_cases_at", "cagpu_stream_refill", "cagpu_episode_metrics_carry_bytes", "cagpu_episode_metrics",
-           "cagpu_step_ex_maps", "cagpu_map_draw")
+           "cagpu_step_ex_maps", "cagpu_map_draw", "cagpu_heading_draw", "cagpu_policy_draw_at")
 
 _lib = None
 
@@ -204,6 +204,8 @@ def lib():
     L.cagpu_policy_draw.argtypes = [PP, PS, PO, PA, C.POINTER(CaPolicyDraw), _P, _P]
     L.cagpu_step_ex_maps.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaStepEx), C.POINTER(CaPolicyDraw), _P]
     L.cagpu_map_draw.argtypes = [C.c_uint64, C.c_int32, _P, _P, C.c_int64, _P, _P]
+    L.cagpu_heading_draw.argtypes = [C.c_uint64, C.c_int32, _P, _P, C.c_int64, _P, _P]
+    L.cagpu_policy_draw_at.argtypes = [C.POINTER(CaPolicyDraw), C.c_int32, _P, _P, _P, C.c_int64, _P, _P]
     L.cagpu_render.argtypes = [PP, PS, C.POINTER(CaMap), C.POINTER(CaRender), _P]
     L.cagpu_render_maps.argtypes = [PP, PS, C.POINTER(CaMapSet), C.POINTER(CaRender), _P]
     L.cagpu_render_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

@@ -188,6 +188,12 @@ class BatchedSim(object):
         self._met = None
         # the case stream (set_case_stream): None = off; dict(c=CaCaseStream, ref, its tensors, every, since, dist)
         self._cstream = None
+        # what a replay needs that the running state does not hold (episode_start): the case rows and headings reset()
+        # loaded, float64 [E, N, 7] (NaN heading: pointed at the goal; NaN rows: never reset; None before the first
+        # reset), the flag words set_plugins gave every slot (host int32 [E, N]; None: never called) and set_map's arguments
+        self._start = None
+        self._plugin_words = None
+        self._map_src = None
 
     # ---------------------------------------------------------------- what the outside reads
     # `state` and the four outputs are those of the step last handed out: reading them goes through sync(), which rewinds a
@@ -347,7 +353,8 @@ class BatchedSim(object):
         bits = (pol << nat.POLICY_SHIFT) | (dyn << nat.DYNAMICS_SHIFT) | (isl * nat.IS_LEARNING) | \
                (stl * nat.STILL_LEARNING)
         cur = self._state["flags"]
-        cur.copy_((cur & (0x3F | nat.ABSENT)) | torch.as_tensor(bits.astype(np.int32), device=self.device))
+        self._plugin_words = bits.astype(np.int32)
+        cur.copy_((cur & (0x3F | nat.ABSENT)) | torch.as_tensor(self._plugin_words, device=self.device))
         self._plugins_ga3c = bool((pol == nat.POL_GA3C_CADRL).any())
         self._has_ga3c = self._plugins_ga3c or (self._draw is not None and self._draw["has_ga3c"])
 
@@ -716,7 +723,7 @@ class BatchedSim(object):
         t_bits = torch.as_tensor(bits.astype(np.int32)).to(self.device)
         d = nat.CaPolicyDraw(cdf=t_cdf.data_ptr(), policy_bits=t_bits.data_ptr(), num_policies=P, ensure=ens, seed=seed)
         has_ga3c = bool((((bits >> nat.POLICY_SHIFT) & 0xF) == nat.POL_GA3C_CADRL).any())
-        self._draw = dict(c=d, ref=C.byref(d), cdf=t_cdf, bits=t_bits, has_ga3c=has_ga3c)
+        self._draw = dict(c=d, ref=C.byref(d), cdf=t_cdf, bits=t_bits, has_ga3c=has_ga3c, pool=bits.copy())
         draw_ref, step_draw = self._draw["ref"], self.lib.cagpu_step_draw
         self._launch = lambda p, s, o, ext, ar, sx, stream: step_draw(p, s, o, ext, ar, sx, draw_ref, stream)
         # (any slot may become a GA3C-CADRL agent at an auto-reset: the network then runs before every step)
@@ -759,6 +766,15 @@ class BatchedSim(object):
         if self._draw is not None:   # episode 0 of the envs this reset touches needs its lottery too
             self._policy_draw_now(m)
         self._keep = [c, h, m]  # keep alive until the stream has consumed them
+        # what was loaded, merged under the mask: episode 0 is the caller's choice and cannot be re-derived (episode_start)
+        c7 = torch.cat([c, (torch.full((self.E, self.N), math.nan, dtype=torch.float64, device=self.device)
+                            if h is None else h.reshape(self.E, self.N)).unsqueeze(-1)], dim=-1)
+        if m is None:
+            self._start = c7
+        else:
+            if self._start is None:
+                self._start = torch.full_like(c7, math.nan)
+            self._start = torch.where((m != 0).reshape(self.E, 1, 1), c7, self._start)
         if self._cstream is not None:   # the reset envs restart at episode 0: their window holds episodes 1 .. W again
             self._stream_refill()
         if self._log is not None:   # the reset envs count their episodes from 0 again: undrained records of theirs are discarded
@@ -801,6 +817,9 @@ class BatchedSim(object):
         seeded by map_seed (`map_seed` property: the key in force); 0: every env keeps its map."""
         self.sync()
         bits = None
+        self._map_src = dict(static_map=None if static_map is None else np.array(static_map, dtype=bool), rows=rows, cols=cols,
+                             cell=cell, num_beams=num_beams, num_to_store=num_to_store, max_range=max_range,
+                             range_res=range_res, min_angle=min_angle, max_angle=max_angle)
         self._maps, self._map_rng, self._env_map = None, None, None
         self._sx.map, self._sx.set = None, None   # (re-pointed below, once the new structs exist)
         self.occ, self.occ_bits, self._occ = None, None, None   # (sized by the map's cell: set_occupancy_grid() again)
@@ -1478,6 +1497,132 @@ class BatchedSim(object):
         out, mt["cursor"] = episode_metrics.drain(mt["vals"], mt["cnts"], mt["head"], mt["cursor"],
                                                   self._handed_out_reset_count())
         return out
+
+    # ---------------------------------------------------------------- replay (replay.py; DESIGN.md "Replay")
+    def episode_start(self, env, episode, _host=None):
+        """The start state of episodes by their ADDRESS: `env` (a local index, as episodes() reports it) and `episode`, ints or
+        int sequences of equal length M -> dict of device tensors: `cases` float64 [M, N, 6], `headings` float64 [M, N] (NaN:
+        pointed at the goal), `policy_bits` int32 [M, N] (bits 6..11 of the flag word; -1 for an absent slot of a draw),
+        `case` int64 [M] (the table row, or the 64-bit index under a case stream), with a map set `map` int64 [M] -- and
+        `plan`, the host-side int64 arrays of replay.plan.  Episode 0 is what reset() loaded (kept); an episode k >= 1 is
+        rebuilt by the kernels' own rules: the fixture table by the row formula or generate_cases_at(stream_case_index),
+        cagpu_heading_draw under a heading_seed, cagpu_policy_draw_at under a policy draw (otherwise the words set_plugins
+        gave the env's slots), cagpu_map_draw.  A pure function of the address: episodes that have not run yet are legal.
+        Reads nothing of the running state (no look-ahead ring is rewound).  ValueError, before anything is launched, where
+        the episode depended on something the batch did not keep (replay.refuse lists the cases)."""
+        from . import replay as rp
+        pl = rp.plan(self, env, episode, **(_host or {}))
+        env, ep = pl["env"], pl["episode"]
+        M, N, dev = len(env), self.N, self.device
+        on_dev = lambda a, dt=torch.int64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev)
+        env_t, ep_t = on_dev(env), on_dev(ep)
+        cases = torch.zeros((M, N, 6), dtype=torch.float64, device=dev)
+        headings = torch.full((M, N), math.nan, dtype=torch.float64, device=dev)
+        first, later = np.flatnonzero(ep == 0), np.flatnonzero(ep != 0)
+        if first.size:
+            kept = self._start.index_select(0, on_dev(env[first]))
+            cases.index_copy_(0, on_dev(first), kept[..., :6].contiguous())
+            headings.index_copy_(0, on_dev(first), kept[..., 6].contiguous())
+        ge, cnt = on_dev(pl["global_env"]), on_dev(ep, torch.int32)
+        if later.size:
+            at = on_dev(later)
+            if self._cstream is not None:
+                st = self._cstream
+                keep = self._keep
+                rows = self.generate_cases_at(on_dev(pl["case"][later]), st["seed"], **st["dist"])
+                self._keep = keep + self._keep
+            else:
+                rows = self._table.index_select(0, on_dev(pl["row"][later]))
+            cases.index_copy_(0, at, rows)
+            if self._ar.heading_seed:
+                g2, c2 = ge.index_select(0, at).contiguous(), cnt.index_select(0, at).contiguous()
+                drawn = torch.empty((later.size, N), dtype=torch.float64, device=dev)
+                nat.check(self.lib.cagpu_heading_draw(int(self._ar.heading_seed), N, g2.data_ptr(), c2.data_ptr(), later.size,
+                                                      drawn.data_ptr(), self._stream()))
+                headings.index_copy_(0, at, drawn)
+        if self._draw is not None and M:
+            present = (cases[..., 5] > 0).to(torch.uint8).contiguous() if self.p.ragged else None
+            bits = torch.empty((M, N), dtype=torch.int32, device=dev)
+            nat.check(self.lib.cagpu_policy_draw_at(self._draw["ref"], N, ge.data_ptr(), cnt.data_ptr(),
+                                                    None if present is None else present.data_ptr(), M, bits.data_ptr(),
+                                                    self._stream()))
+        else:
+            words = np.zeros((M, N), np.int32) if self._plugin_words is None else self._plugin_words[env]
+            bits = on_dev(words & nat.POLICY_DRAW_BITS, torch.int32)
+        out = {"cases": cases, "headings": headings, "policy_bits": bits, "case": on_dev(pl["case"]), "plan": pl}
+        if self._maps is not None:
+            out["map"] = self._episode_maps(env_t, ep_t)
+            if M and bool((out["map"] < 0).any()):
+                raise ValueError("replay: the map of a requested episode is not known any more (episodes() reports it as -1: "
+                                 "the map set's key was replaced after that map was drawn)")
+        return out
+
+    def _replay_child(self, start, record, capacity):
+        """the batch that runs the M episodes of `start` (episode_start) alone: this sim's CaParams, sort mode, ragged and
+        pipeline switch, GA3C-CADRL weights and assignment, map (a set: the same stack, env_map = the episodes' maps, no key)
+        and occupancy-grid settings; its fixture table is the M case rows with env_id_offset 0 and case_stride M -- child env
+        i auto-resets into row i again, so that its terminal step runs the kernels' " final" instantiations and the final
+        record, the log and the metrics produce the replay's records -- no heading seed, no policy draw, no case stream"""
+        pl = start["plan"]
+        env, M, N, dev = pl["env"], len(pl["env"]), self.N, self.device
+        ps = nat.CaParams.from_buffer_copy(self.p)
+        ps.num_envs = M
+        child = BatchedSim(ps, device=dev, pipeline=self.pipeline)
+        w = (np.zeros((M, N), np.int32) if self._plugin_words is None else self._plugin_words[env]).astype(np.int64)
+        child.set_plugins((w >> nat.POLICY_SHIFT) & 0xF, (w >> nat.DYNAMICS_SHIFT) & 0xF, (w & nat.IS_LEARNING) != 0,
+                          (w & nat.STILL_LEARNING) != 0)
+        for idx, (_, ts) in self._nets.items():   # the parent's weights and packed planes, a packing list of the child's own
+            ts2 = dict(ts)
+            ts2["rows_scratch"] = torch.empty((M * N + 6,), dtype=torch.int32, device=dev)
+            net = nat.CaNet(**{f: ts2[f].data_ptr() for f in nat.NET_FIELDS + ("rows_scratch", "packed")})
+            child._nets[idx] = (net, ts2)
+            if ts is self._net_tensors:
+                child._net, child._net_tensors = net, ts2
+        if self._nets:
+            child.ga3c_fused = self.ga3c_fused
+            if self.ga3c_value is not None:
+                child.ga3c_value = torch.zeros((M, N), dtype=torch.float32, device=dev)
+            if self._agent_net is not None:
+                child._agent_net = self._agent_net.index_select(0, torch.as_tensor(env, device=dev)).contiguous()
+        if self._map_src is not None:
+            if self._maps is not None:
+                child.set_map(env_map=start["map"].cpu().numpy(), map_seed=0, **self._map_src)
+            else:
+                child.set_map(**self._map_src)
+            if self._occ is not None:
+                child.set_occupancy_grid(self._occ.x_width, self._occ.y_width,
+                                         packed=False if self.occ_bits is None else (True if self.occ is None else "both"))
+        child.set_fixture_table(start["cases"], env_id_offset=0, case_stride=M, heading_seed=0)
+        child.keep_final(True)
+        child.log_episodes(capacity=capacity)
+        if record:
+            child.record_trajectories()
+            child.measure_episodes(capacity=capacity + 1, keep_tape=True)
+        # the start state: a first reset points every agent at its goal with the DEVICE's arctan2, as an auto-reset without
+        # heading seed does; a second one hands those headings back where none was drawn or kept
+        child.reset(start["cases"])
+        h = start["headings"]
+        child.reset(start["cases"], headings=torch.where(torch.isnan(h), child._state["heading"], h))
+        # the flag words: bits 6..11 of present slots from the address, no plan (it belongs to the policy it was made for);
+        # dynamics bits and the words of absent slots are the plugin words set above
+        fl = child._state["flags"]
+        here = (fl & nat.ABSENT) == 0
+        fl.copy_(torch.where(here, (fl & ~(nat.POLICY_DRAW_BITS | nat.PLAN_VALID)) | (start["policy_bits"] & nat.POLICY_DRAW_BITS), fl))
+        child._has_ga3c = child._plugins_ga3c = bool(self._has_ga3c)
+        child.observe()   # (column 0 follows the bits)
+        return child
+
+    def replay(self, env, episode, record=True, max_steps=None, keep_outputs=False, _host=None):
+        """Run episodes again from their address (episode_start) -> replay.Replay: a child batch of the M episodes alone
+        (_replay_child) is stepped until every one of them has ended, and its final record, episode log, metrics and -- with
+        `record` -- trajectory tape are the replay's, bit for bit what the original run gave or would have given.
+        max_steps: default, the most steps any of the M cases can take under max_time_ratio; a replay that needs more
+        raises CagpuError.  keep_outputs: also keep obs / rewards / done of every step (Replay.outputs).  The child runs
+        under the CURRENT CaParams: an update_params() between the original episode and the replay is the caller's
+        business.  This sim is not touched: no state, output, statistic or tape of it changes, and a look-ahead ring
+        that has run ahead is not rewound."""
+        from . import replay as rp
+        return rp.run(self, env, episode, record=record, max_steps=max_steps, keep_outputs=keep_outputs, host=_host)
 
     # ---------------------------------------------------------------- the trajectory tape (include/cagpu.h CaTraj)
     TRAJ_BLOCK_BYTES = 8 << 20   # step(): slots are taken from blocks of about this size (at most 64 slots), not a tensor per step

@@ -761,6 +761,7 @@ __device__ __forceinline__ void reset_lane(Lane& r, const double* c, const bool 
 }
 
 #include "cagpu_rules.inc"
+#include "cagpu_replay.inc"
 
 // MSET: the n-step form (MULTI) also runs the map-set code of the single-step form -- the per-env grid of A3, the map draw
 // of an auto-reset.  A template flag that only a set launch with n_steps > 1 selects (launch_main4): every other
@@ -2104,12 +2105,18 @@ static int check_map_set(const CaMapSet* set, const char* who) {
 }
 
 // the argument checks of the policy draw (CaPolicyDraw), shared by cagpu_step_draw and cagpu_policy_draw
-static int check_draw(const CaPolicyDraw* d, const CaAutoReset* ar, const char* who) {
+// (check_draw_pool: what they reject of d alone -- all cagpu_policy_draw_at, which has no CaAutoReset, can be held to)
+static int check_draw_pool(const CaPolicyDraw* d, const char* who) {
   if (!d->cdf || !d->policy_bits) return fail(CA_EINVAL, "%s: NULL CaPolicyDraw.cdf or CaPolicyDraw.policy_bits", who);
   if (d->num_policies < 1 || d->num_policies > 8) return fail(CA_EINVAL, "%s: CaPolicyDraw.num_policies must be in 1..8", who);
   if (d->ensure < -1 || d->ensure >= d->num_policies)
     return fail(CA_EINVAL, "%s: CaPolicyDraw.ensure must be -1 or a pool index below num_policies", who);
   if (d->seed == 0) return fail(CA_EINVAL, "%s: CaPolicyDraw.seed must not be 0", who);
+  return CA_OK;
+}
+static int check_draw(const CaPolicyDraw* d, const CaAutoReset* ar, const char* who) {
+  const int rp = check_draw_pool(d, who);
+  if (rp) return rp;
   if (!ar) return fail(CA_EINVAL, "%s: a CaPolicyDraw without a CaAutoReset (no table: nothing is ever drawn)", who);
   if (d->seed == ar->heading_seed)
     return fail(CA_EINVAL, "%s: CaPolicyDraw.seed equals CaAutoReset.heading_seed (an agent's heading and policy would be the same uniform)", who);
@@ -2276,6 +2283,38 @@ int cagpu_map_draw(uint64_t seed, int32_t num_maps, const int64_t* env_ids, cons
   const unsigned grid = static_cast<unsigned>((n + 255) / 256);
   hipLaunchKernelGGL(map_draw_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), seed, num_maps, env_ids, counts,
                      static_cast<long>(n), out);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
+}
+
+int cagpu_heading_draw(uint64_t heading_seed, int32_t num_agents, const int64_t* env_ids, const int32_t* counts, int64_t n,
+                       double* out, void* stream) {
+  if (!env_ids || !counts || !out || heading_seed == 0 || num_agents < 1 || num_agents > big::NT_MAX || n < 0)
+    return fail(CA_EINVAL, "cagpu_heading_draw: NULL pointer, heading_seed == 0, num_agents outside 1..1024 or n < 0%s");
+  if (n == 0) return CA_OK;
+  const long total = static_cast<long>(n) * num_agents;
+  const unsigned grid = static_cast<unsigned>((total + 255) / 256);
+  hipLaunchKernelGGL(heading_draw_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), heading_seed, num_agents,
+                     env_ids, counts, total, out);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
+}
+
+int cagpu_policy_draw_at(const CaPolicyDraw* d, int32_t num_agents, const int64_t* env_ids, const int32_t* counts,
+                         const uint8_t* present, int64_t n, uint32_t* out_bits, void* stream) {
+  if (!d || !env_ids || !counts || !out_bits || num_agents < 1 || num_agents > big::NT_MAX || n < 0)
+    return fail(CA_EINVAL, "cagpu_policy_draw_at: NULL pointer, num_agents outside 1..1024 or n < 0%s");
+  const int rd = check_draw_pool(d, "cagpu_policy_draw_at");
+  if (rd) return rd;
+  if (n == 0) return CA_OK;
+  DrawAtArgs k;
+  std::memset(&k, 0, sizeof(k));
+  k.cdf = d->cdf; k.bits = d->policy_bits; k.seed = d->seed; k.env_ids = env_ids; k.counts = counts; k.present = present;
+  k.out = out_bits; k.n = static_cast<long>(n); k.N = num_agents; k.P = d->num_policies; k.ensure = d->ensure;
+  const unsigned grid = static_cast<unsigned>(n < 65536 ? n : 65536);   // (one wave per pair; longer lists stride)
+  hipLaunchKernelGGL(policy_draw_at_kernel, dim3(grid), dim3(64), 0, static_cast<hipStream_t>(stream), k);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
   return CA_OK;

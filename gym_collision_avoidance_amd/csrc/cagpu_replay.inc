@@ -1,0 +1,45 @@
+// gym_collision_avoidance_amd/csrc/cagpu_replay.inc -- included by cagpu.hip (inside its anonymous namespace, after
+// cagpu_rules.inc).
+//
+// The draw rules of an auto-reset for ARBITRARY (global env id, episode) pairs: what cagpu_map_draw is for the map of a map
+// set, for the training-mode heading (cagpu_heading_draw) and the policy draw (cagpu_policy_draw_at).  Both kernels call
+// the device functions the step kernels call -- reset_heading (cagpu_rules.inc) and policy_draw_word (cagpu.hip) -- so an
+// episode's start state can be rebuilt after the fact from its address alone (DESIGN.md "Replay"); no rule is restated here.
+
+// one thread per (pair, slot): out[i, a] = reset_heading of slot a of env env_ids[i] at its counts[i]-th auto-reset
+__global__ __launch_bounds__(256) void heading_draw_kernel(const unsigned long long seed, const int N, const int64_t* env_ids,
+                                                            const int32_t* counts, const long total, double* out) {
+  const long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long pair = i / N;
+  const int a = static_cast<int>(i - pair * N);
+  KArgs k;  // (reset_heading reads these two members only)
+  k.heading_seed = seed;
+  k.env_id_offset = env_ids[pair];
+  out[i] = reset_heading(k, 0, counts[pair], a);
+}
+
+// one wave per pair (the ensure rule counts the pair's present slots): lane l settles slots l, l + 64, ...
+struct DrawAtArgs {
+  const double* cdf;
+  const uint32_t* bits;
+  unsigned long long seed;
+  const int64_t* env_ids;
+  const int32_t* counts;
+  const uint8_t* present;  // [n, N] or nullptr: every slot
+  uint32_t* out;           // [n, N]
+  long n;
+  int32_t N, P, ensure;
+};
+__global__ __launch_bounds__(64) void policy_draw_at_kernel(const DrawAtArgs d) {
+  const int lane = threadIdx.x;
+  for (long pair = blockIdx.x; pair < d.n; pair += gridDim.x) {
+    const uint8_t* pr = d.present ? d.present + pair * d.N : nullptr;
+    const auto present = [&](const int j) { return !pr || pr[j] != 0; };
+    const long ge = d.env_ids[pair];
+    const int k = d.counts[pair];
+    for (int a = lane; a < d.N; a += 64)
+      d.out[pair * d.N + a] = present(a) ? (policy_draw_word(d.cdf, d.bits, d.P, d.ensure, d.seed, ge, k, a, d.N, present, 0u) & 0xFC0u)
+                                         : 0xFFFFFFFFu;
+  }
+}

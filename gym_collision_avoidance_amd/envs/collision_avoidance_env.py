@@ -1242,6 +1242,25 @@ class CollisionAvoidanceEnv(Env):
             out["metrics_dropped"] = int(met["dropped"])
         return out
 
+    def replay(self, env_ids, episodes, **kw):
+        """Run episodes of the batch again from their address -- `env_ids` (this shard's env indices, as episode_log()
+        reports them) and `episodes`, ints or sequences of equal length -- on a child batch (core.BatchedSim.replay;
+        keywords record=True, max_steps=None, keep_outputs=False): the log named the episode that failed, this shows it.
+        -> replay.Replay: `record`, `final_observation`, `trajectories()`, `histories(i)`, `frames(i)` and `save_plots(dir)`,
+        which writes the reference's `{test_case:03d}_{policy}_{N}agents.png` (and `collisions/` for the episodes that
+        collided).  Neither the batch nor its look-ahead ring is touched.  ValueError where the episode depended on
+        something the batch did not keep: external or user Python policies, custom Dynamics, stochastic RVO draws, sensor
+        variants, an episode >= 1 without auto-reset, a map the log reports as -1."""
+        if self._sim is None:
+            raise RuntimeError("call reset() before replay()")
+        host = dict(host_policies=bool(self._host_policies) or bool(self._host_by_env and any(self._host_by_env)),
+                    host_dynamics=bool(self._host_dynamics) or bool(self._hostdyn_by_env and any(self._hostdyn_by_env)))
+        rep = self._sim.replay(env_ids, episodes, _host=host, **kw)
+        rep.plot_policy = self.plot_policy_name or self.agents[0].policy.str
+        rep.plot_case_offset = int(self.test_case_index)
+        rep.plot_defaults = self._render_defaults({})
+        return rep
+
     def _ring_len(self, sim):
         """the longest look-ahead ring: `lookahead` if given, else what the byte budget holds of the batch's slots (with the
         final record every slot carries its final block as well: the same budget, a shorter ring)"""

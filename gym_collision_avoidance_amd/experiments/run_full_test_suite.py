@@ -79,7 +79,7 @@ def run_suite(policy="RVO", num_agents=4, test_cases=None, device="cuda:0", max_
 
 
 def run_suite_logged(policy="RVO", num_agents=4, test_cases=None, num_envs=None, device="cuda:0", chunk=256, max_steps=200000,
-                     metrics=False, static_map=None):
+                     metrics=False, static_map=None, plot_failures=None):
     """run_suite() through the on-device episode log (CollisionAvoidanceEnv.log_episodes): `num_envs` envs (default
     min(number of cases, 64)) walk the table of `test_cases` with the on-device auto-reset -- env e runs cases e,
     e + num_envs, ... --, env.rollout() advances the batch `chunk` steps per call (one fused launch where every policy is
@@ -88,7 +88,10 @@ def run_suite_logged(policy="RVO", num_agents=4, test_cases=None, num_envs=None,
     (bit for bit where a case is the first episode of its env; later episodes start from the device's own arctan2).
     metrics=True: the episode metrics are measured as well (CollisionAvoidanceEnv.measure_episodes, a transient tape) and
     every row gains `path_length`, `min_gap`, `turn_sum` (float arrays per agent) and `close_steps` (int array).
-    static_map (under Config.USE_STATIC_MAP): as in run_suite -- the fused rollouts test the same walls as its single steps."""
+    static_map (under Config.USE_STATIC_MAP): as in run_suite -- the fused rollouts test the same walls as its single steps.
+    plot_failures=DIR: after the run every case whose outcome is not "all_at_goal" is replayed from its (env, episode)
+    address in ONE env.replay() call and its plot written to DIR (the reference's file names, `collisions/` for the cases
+    that collided) -- nothing of the run itself is recorded for it."""
     import pandas as pd
     spec = policies[policy]
     cases = list(range(len(tc.fixture_table(num_agents)))) if test_cases is None else list(test_cases)
@@ -144,6 +147,12 @@ def run_suite_logged(policy="RVO", num_agents=4, test_cases=None, num_envs=None,
                      "all_at_goal": bool(r["all_at_goal"]), "any_stuck": bool(r["any_stuck"]), "outcome": str(r["outcome"])})
         if metrics:
             rows[-1].update({n: np.array(r[n]) for n in ("path_length", "min_gap", "turn_sum", "close_steps")})
+    if plot_failures is not None:
+        failed = [first[j] for j in range(len(cases)) if str(first[j]["outcome"]) != "all_at_goal"]
+        if failed:
+            rep = env.replay([int(r["env"]) for r in failed], [int(r["episode"]) for r in failed])
+            rep.plot_policy = policy
+            rep.save_plots(plot_failures, test_cases=cases)
     return pd.DataFrame(rows)
 
 

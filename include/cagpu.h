@@ -809,6 +809,29 @@ int cagpu_step_draw(const CaParams *p, const CaState *s, const CaOut *o, const d
 int cagpu_policy_draw(const CaParams *p, const CaState *s, const CaOut *o, const CaAutoReset *ar, const CaPolicyDraw *d,
                       const uint8_t *env_mask, void *stream);
 
+/* THE DRAWS OF AN EPISODE'S ADDRESS (additive to v12): the two auto-reset rules above for ARBITRARY (global env id, episode)
+ * pairs, as cagpu_map_draw gives the map of a map set and cagpu_generate_cases_at the scenario of a case stream -- with
+ * them the start state of any episode of a batch is rebuilt from (seed, global env id, episode number) alone.  Both kernels
+ * call the device functions the step kernels call (no rule is stated twice).  env_ids device int64 [n], counts device
+ * int32 [n]; pair i is the env with global id env_ids[i] at its counts[i]-th auto-reset (counts[i] >= 1 for an auto-reset;
+ * cagpu_policy_draw's episode 0 is counts[i] = 0).
+ *   cagpu_heading_draw    out[i, a] (device double [n, num_agents]) = the heading slot a takes under
+ *                         CaAutoReset.heading_seed = heading_seed: uniform in [-pi, pi).  One thread per (pair, slot).
+ *   cagpu_policy_draw_at  steps 1 and 2 of CaPolicyDraw's rule: out_bits[i, a] = policy_bits[j] & 0xFC0 of the pool entry
+ *                         slot a ends up with; `present` (device uint8 [n, num_agents], NULL: every slot) names the slots
+ *                         that hold an agent -- the ensure rule counts over them -- and an absent slot gets 0xFFFFFFFF.
+ *                         One wave per pair.
+ * n == 0: nothing is launched.  CA_EINVAL, nothing launched: a NULL pointer (present excepted), heading_seed == 0, n < 0,
+ * num_agents outside 1..1024, and of d what cagpu_step_draw rejects of d alone (cdf / policy_bits NULL, num_policies
+ * outside 1..8, ensure outside -1 .. P - 1, seed == 0).  env_ids and counts live on the device and are not read by the
+ * host, as in cagpu_map_draw: an id is taken as the 64-bit counter pair (lo, hi) it spells and a count as the 32-bit word
+ * it spells -- whoever holds them on the host (BatchedSim.episode_start) rejects ids outside [0, 2^32) and negative
+ * counts there. */
+int cagpu_heading_draw(uint64_t heading_seed, int32_t num_agents, const int64_t *env_ids, const int32_t *counts, int64_t n,
+                       double *out, void *stream);
+int cagpu_policy_draw_at(const CaPolicyDraw *d, int32_t num_agents, const int64_t *env_ids, const int32_t *counts,
+                         const uint8_t *present, int64_t n, uint32_t *out_bits, void *stream);
+
 /* The policy query of the NEXT step ahead of time (collision_avoidance_env.py:305-323 for the built-in RVO policy):
  * fills s->next_action from the CURRENT state and sets CA_PLAN_VALID, without stepping.  cagpu_step / cagpu_rollout keep
  * the plan up to date by themselves; this entry point exists for states that did not come out of a step (the reset state
