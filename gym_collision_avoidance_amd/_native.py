@@ -103,6 +103,11 @@ class CaPolicyDraw(C.Structure):
     _fields_ = [("cdf", _P), ("policy_bits", _P), ("num_policies", C.c_int32), ("ensure", C.c_int32), ("seed", C.c_uint64)]
 
 
+class CaActionTape(C.Structure):
+    """an action tape (cagpu_step_tape): slot t of `actions` is step t's [E, N, 2]; include/cagpu.h states the rules"""
+    _fields_ = [("actions", _P), ("step_stride", C.c_int64)]
+
+
 class CaCaseStream(C.Structure):
     """a case stream (cagpu_stream_refill): the window table of a CaAutoReset and what keeps it ahead of the envs;
     include/cagpu.h states the rule.  side_ranges is a HOST pointer: whoever stores it keeps that array alive"""
@@ -152,7 +157,7 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_step_log", "cagpu_rollout_log", "cagpu_step_ex", "cagpu_step_draw", "cagpu_policy_draw",
            "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes", "cagpu_ga3c_query", "cagpu_ga3c_value",
            "cagpu_generate_cases_at", "cagpu_stream_refill", "cagpu_episode_metrics_carry_bytes", "cagpu_episode_metrics",
-           "cagpu_step_ex_maps", "cagpu_map_draw", "cagpu_heading_draw", "cagpu_policy_draw_at")
+           "cagpu_step_ex_maps", "cagpu_map_draw", "cagpu_heading_draw", "cagpu_policy_draw_at", "cagpu_step_tape")
 
 _lib = None
 
@@ -203,6 +208,7 @@ def lib():
     L.cagpu_step_draw.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaStepEx), C.POINTER(CaPolicyDraw), _P]
     L.cagpu_policy_draw.argtypes = [PP, PS, PO, PA, C.POINTER(CaPolicyDraw), _P, _P]
     L.cagpu_step_ex_maps.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaStepEx), C.POINTER(CaPolicyDraw), _P]
+    L.cagpu_step_tape.argtypes = [PP, PS, PO, C.POINTER(CaActionTape), PA, C.POINTER(CaStepEx), C.POINTER(CaPolicyDraw), _P]
     L.cagpu_map_draw.argtypes = [C.c_uint64, C.c_int32, _P, _P, C.c_int64, _P, _P]
     L.cagpu_heading_draw.argtypes = [C.c_uint64, C.c_int32, _P, _P, C.c_int64, _P, _P]
     L.cagpu_policy_draw_at.argtypes = [C.POINTER(CaPolicyDraw), C.c_int32, _P, _P, _P, C.c_int64, _P, _P]

@@ -194,6 +194,8 @@ class BatchedSim(object):
         self._start = None
         self._plugin_words = None
         self._map_src = None
+        # rollout(keep_steps=True) with keep_final() on: every slot's final block (final_obs [n, E, N, W], final_flags [n, E, N])
+        self.kept_final = None
 
     # ---------------------------------------------------------------- what the outside reads
     # `state` and the four outputs are those of the step last handed out: reading them goes through sync(), which rewinds a
@@ -1023,31 +1025,90 @@ class BatchedSim(object):
             self._apply_sensor_variants()
         return self._obs, self._rewards, self._game_over
 
-    def rollout(self, n_steps, ext_actions=None):
+    def _action_tape(self, ext_actions, n):
+        """rollout()'s external actions -> (float64 device tensor or None, doubles from one step's slot to the next): 0 for
+        [E, N, 2], ONE slot held for all steps; E * N * 2 for an action tape [T, E, N, 2], T >= n, slot t for step t.
+        Converted once (dtype, device, layout), like every array that goes to the library."""
+        if ext_actions is None:
+            return None, 0
+        shape = tuple(getattr(ext_actions, "shape", None) or np.shape(ext_actions))
+        held, E, N = (self.E, self.N, 2), self.E, self.N
+        if shape != held and not (len(shape) == 4 and shape[1:] == held and shape[0] >= n):
+            raise ValueError("rollout: ext_actions must be [E, N, 2] = %r (one action held for all steps) or an action tape "
+                             "[T, E, N, 2] with T >= n_steps = %d, got %r" % (held, n, shape))
+        return self._dev(ext_actions, torch.float64), (0 if len(shape) == 3 else E * N * 2)
+
+    def rollout(self, n_steps, ext_actions=None, keep_steps=False):
+        """n_steps steps in ONE launch (cagpu_step_ex's n_steps) -> the last step's (obs, rewards, game_over).
+        ext_actions: [E, N, 2], held for all steps, or an ACTION TAPE [T, E, N, 2] (T >= n_steps): step t of the call plays
+        slot t (cagpu_step_tape) -- the step of the CALL, not of the episode: an env that auto-resets in step t plays slot
+        t + 1 as the first action of its next episode.  Entries of agents that are not queried (internal policies, done
+        agents, absent slots) are never read.  Where the batch needs work between two steps (a GA3C-CADRL network, stochastic
+        RVO draws) the steps are single launches and step t is handed slot t: the same results, one launch per step.
+        keep_steps: every step keeps its outputs (a ring launch, CaStepEx.ring, into newly allocated tensors) and the call
+        returns (obs [n, E, N, W], rewards [n, E, N], done [n, E, N], game_over [n, E]); `obs` / `rewards` / `done` /
+        `game_over` afterwards show the last slot.  With keep_final() on every slot has its own final block: `kept_final` =
+        (final_obs [n, E, N, W], final_flags [n, E, N]), rows valid where the slot's game_over is set (None after every other
+        rollout); `final_obs` / `final_flags` show the last slot's.  The trajectory tape, the episode log, maps, the policy
+        draw, the case stream and the metrics ride on either form as on rollout(n)."""
         self.sync()
+        n = int(n_steps)
         # (CaState.ext_state belongs to the ONE step() call that was given it: never re-applied by the steps of a rollout)
         self._cs.ext_state, self._ext_state = None, None
+        e, stride = self._action_tape(ext_actions, n)
+        self.kept_final = None
         if self._has_ga3c or self._rvo is not None:  # the network / the stochastic RVO draws run between steps
-            for _ in range(int(n_steps)):
-                self.step(ext_actions)
+            kept = []
+            for t in range(n):
+                self.step(e if stride == 0 else e[t])
+                if keep_steps:   # (torch.stack copies at the end: until then a step that writes in place must not reach them)
+                    own = (lambda x: x) if self.fresh_outputs else (lambda x: x.clone())
+                    kept.append(tuple(own(x) for x in (self._obs, self._rewards, self._done, self._game_over) +
+                                      ((self._fin_obs, self._fin_flags) if self._fin_on else ())))
+            if keep_steps:
+                cols = [torch.stack(c) for c in zip(*kept)]
+                if self._fin_on:
+                    self.kept_final = (cols[4], cols[5])
+                return cols[0], cols[1], cols[2], cols[3]
             return self._obs, self._rewards, self._game_over
-        e = self._dev(ext_actions, torch.float64)
-        if self.fresh_outputs:
+        if self.fresh_outputs and not keep_steps:
             self._new_outputs()
         if self._cstream is not None:
             self._stream_refill()
         # the n steps' CaStepEx: the map or set of a single step, the tape's own chunk, the single-step final block -- it ends up holding every
         # env's most recent terminal record of the launch -- and the log, every ending in its own slot
-        chunk, ct = self._traj_chunk(int(n_steps)) if self._traj_on else (None, None)
-        sx = nat.CaStepEx(n_steps=int(n_steps), map=self._sx.map, set=self._sx.set, traj=None if ct is None else C.addressof(ct),
-                          fin=self._sx.fin, log=self._sx.log)
-        nat.check(self._launch_n(self._p_ref, self._cs_ref, self._co_ref, None if e is None else e.data_ptr(), self._ar_ref,
-                                C.byref(sx), self._stream_handle()))
+        chunk, ct = self._traj_chunk(n) if self._traj_on else (None, None)
+        co_ref, fin = self._co_ref, self._sx.fin
+        if keep_steps:   # a ring launch without a rewind point: the look-ahead ring's layout, every slot its final block
+            ring, fin_ring, cf, co, _ = self._ring_layout(n)
+            co_ref, fin = C.byref(co), None if cf is None else C.addressof(cf)
+        sx = nat.CaStepEx(n_steps=n, ring=1 if keep_steps else 0, map=self._sx.map, set=self._sx.set,
+                          traj=None if ct is None else C.addressof(ct), fin=fin, log=self._sx.log)
+        if stride:
+            tape = nat.CaActionTape(actions=e.data_ptr(), step_stride=stride)
+            nat.check(self.lib.cagpu_step_tape(self._p_ref, self._cs_ref, co_ref, C.byref(tape), self._ar_ref, C.byref(sx),
+                                               None if self._draw is None else self._draw["ref"], self._stream_handle()))
+        else:
+            nat.check(self._launch_n(self._p_ref, self._cs_ref, co_ref, None if e is None else e.data_ptr(), self._ar_ref,
+                                     C.byref(sx), self._stream_handle()))
         if chunk is not None:
             self._traj_commit(chunk)
             if self._met is not None:
                 self._met_process()
-        self._keep = [e]
+        self._keep = [e]   # (the tape stays alive until the next launch is queued behind this one)
+        if keep_steps:
+            # the last slot becomes the simulator's current outputs: the caller's own where the next step writes new tensors
+            # anyway (fresh_outputs), a copy where it writes in place
+            own = (lambda x: x) if self.fresh_outputs else (lambda x: x.clone())
+            self._obs, self._rewards, self._done, self._game_over = (own(x[n - 1]) for x in ring)
+            self._co.obs, self._co.rewards, self._co.done, self._co.game_over = (
+                self._obs.data_ptr(), self._rewards.data_ptr(), self._done.data_ptr(), self._game_over.data_ptr())
+            if fin_ring is not None:
+                self.kept_final = fin_ring
+                self._fin_obs, self._fin_flags = own(fin_ring[0][n - 1]), own(fin_ring[1][n - 1])
+                self._cf.obs, self._cf.flags = self._fin_obs.data_ptr(), self._fin_flags.data_ptr()
+            self._apply_sensor_variants()
+            return ring
         self._apply_sensor_variants()
         return self._obs, self._rewards, self._game_over
 
@@ -1170,24 +1231,36 @@ class BatchedSim(object):
                 0 if ar is None else int(ar.heading_seed), 0 if ar is None else C.addressof(ar),
                 int(self._sx.map or 0), int(self._sx.set or 0))
 
-    def _la_prepare(self, k):
-        la, E, N, dev = self._la, self.E, self.N, self.device
-        if la["fresh"] or la["ring"] is None or la["ring"][0].shape[0] != k:
+    def _ring_layout(self, k, ring=None, fin_ring=None):
+        """What a ring launch of k steps (CaStepEx.ring) writes into, stated once for the look-ahead ring and for
+        rollout(keep_steps=True) -> (ring, fin_ring, cf, co, slots): the four output tensors [k, ...] (`ring` / `fin_ring`
+        given: those are used again), the final blocks and their CaFinal where keep_final() is on (None, None otherwise),
+        the CaOut that names slot 0 and the per-slot views handed out later."""
+        E, N, dev = self.E, self.N, self.device
+        if ring is None:
             ring = (torch.empty((k, E, N, self.W), dtype=torch.float32, device=dev), torch.empty((k, E, N), dtype=torch.float32, device=dev),
                     torch.empty((k, E, N), dtype=torch.uint8, device=dev), torch.empty((k, E), dtype=torch.uint8, device=dev))
-        else:
-            ring = la["ring"]           # (fresh=False: ONE persistent ring, a slot is overwritten k steps later)
         obs, rew, done, over = ring
-        fin_ring, cf = None, None
+        cf = None
         if self._fin_on:      # every slot carries its final block (rows valid where the slot's game_over is set)
-            fin_ring = la.get("fin_ring")
-            if la["fresh"] or fin_ring is None or fin_ring[0].shape[0] != k:
+            if fin_ring is None:
                 fin_ring = (torch.empty((k, E, N, self.W), dtype=torch.float32, device=dev),
                             torch.empty((k, E, N), dtype=torch.int32, device=dev))
             cf = nat.CaFinal(obs=fin_ring[0].data_ptr(), flags=fin_ring[1].data_ptr())
+        else:
+            fin_ring = None
         co = nat.CaOut.from_buffer_copy(self._co)   # (the ring's own CaOut: the workspace of self._co, no actions / orca_vel record)
         co.actions, co.orca_vel = None, None
         co.obs, co.rewards, co.done, co.game_over = obs.data_ptr(), rew.data_ptr(), done.data_ptr(), over.data_ptr()
+        # (the kernels write 0 / 1 bytes: reinterpreted as bool without a conversion kernel)
+        slots = list(zip(obs.unbind(0), rew.unbind(0), done.view(torch.bool).unbind(0), over.view(torch.bool).unbind(0)))
+        return ring, fin_ring, cf, co, slots
+
+    def _la_prepare(self, k):
+        la = self._la
+        # (fresh=False: ONE persistent ring, a slot is overwritten k steps later)
+        again = lambda r: r if (not la["fresh"] and r is not None and r[0].shape[0] == k) else None
+        ring, fin_ring, cf, co, slots = self._ring_layout(k, again(la["ring"]), again(la.get("fin_ring")))
         ar_ref = self._ar_ref
         # the rewind point = the state BEFORE the k steps: stored by the pipelined n-step kernel itself as it loads its
         # tiles (snapshot_delta: the snapshot slab has the state slab's layout); by one device copy in front of the launch
@@ -1199,8 +1272,6 @@ class BatchedSim(object):
             if rc < 0:
                 nat.check(rc)
             in_kernel = la["in_kernel"][key] = rc == 1
-        # (the kernels write 0 / 1 bytes: reinterpreted as bool without a conversion kernel)
-        slots = list(zip(obs.unbind(0), rew.unbind(0), done.view(torch.bool).unbind(0), over.view(torch.bool).unbind(0)))
         sx = nat.CaStepEx(n_steps=k, ring=1, snapshot_delta=(la["snap"].data_ptr() - self._slab.data_ptr()) if in_kernel else 0,
                           map=self._sx.map, set=self._sx.set, fin=None if cf is None else C.addressof(cf), log=self._sx.log)
         return dict(k=k, key=key, ring=ring, co=co, co_ref=C.byref(co), ar_ref=ar_ref, in_kernel=in_kernel, slots=slots,

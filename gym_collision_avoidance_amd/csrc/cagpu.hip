@@ -105,6 +105,10 @@ struct KArgs {
   const uint32_t* draw_bits;
   unsigned long long draw_seed;
   int32_t draw_n, draw_ensure;
+  // action tape (cagpu_step_tape; 0 everywhere else): doubles from the slot `ext` names to the slot of the next step.  Step t of
+  // an n-step launch reads ext + t * ext_stride (a kernel argument times the loop counter: scalar registers); where a rollout
+  // is n launches the host advances `ext` itself (ring_advance).  Appended, like the draw
+  int64_t ext_stride;
 };
 
 // One agent's share of an episode-log record (CaEpLog): env e ends its episode number `ep` (its reset count before the
@@ -795,6 +799,7 @@ __global__ __launch_bounds__(NT, MULTI ? (NC == 20 ? 2 : 4) : 1) void ca_kernel(
   float* obs_tile = k.o.obs + tile_base * (6 + 7 * p.max_obs);  // the tile's observation rows (uniform: scalar arithmetic)
   long ring_a = 0, ring_e = 0;  // n-step kernel: this step's slot of the caller's output ring (cagpu_rollout_ring), in elements
   long traj_a = 0, traj_e = 0;  // ... and of the trajectory tape (CaTraj), which advances in a plain rollout too
+  int step = 0;                 // the step of the launch (n-step kernel): an action tape's slot (cagpu_step_tape)
   long tile_cnt = static_cast<long>(p.num_envs) * N - tile_base;
   if (tile_cnt > tile_n) tile_cnt = tile_n;
 
@@ -1165,7 +1170,9 @@ LP1_UNROLL
             r.gy = r.py;
             statics_dirty = true;
           } else if (k.ext) {
-            ext_policy_action(pol, k.ext[2 * i], k.ext[2 * i + 1], r.ps, p.max_heading_change, spd, dh);
+            // (this step's slot of an action tape: a kernel argument times the loop counter, uniform; stride 0 without one)
+            const double* const ex = MULTI ? k.ext + step * k.ext_stride : k.ext;
+            ext_policy_action(pol, ex[2 * i], ex[2 * i + 1], r.ps, p.max_heading_change, spd, dh);
           }
         }
         const float a0f = static_cast<float>(spd), a1f = static_cast<float>(dh);  // float32 `all_actions`
@@ -1590,7 +1597,7 @@ LP1_UNROLL
   };
   if (MULTI) {
     const int n_steps = (k.mode == MODE_STEP) ? k.n_steps : 1;
-    for (int step = 0; step < n_steps; ++step) {
+    for (step = 0; step < n_steps; ++step) {
       one_step();
       obs_tile += k.ring_obs;  // (0 unless the caller keeps every step's outputs: cagpu_rollout_ring)
       ring_a += k.ring_agent;
@@ -1736,6 +1743,7 @@ void ring_advance(KArgs& k) {
   if (k.traj_ep) k.traj_ep += k.p.num_envs;
   if (k.fin_obs) k.fin_obs += k.ring_obs;        // (the final record advances with the outputs: not in a plain rollout)
   if (k.fin_flags) k.fin_flags += k.ring_agent;
+  if (k.ext) k.ext += k.ext_stride;  // (an action tape's next slot; 0 for a held action)
 }
 
 // what a map or map-set launch adds to cagpu_last_kernel(): " set" where the n-step kernels' MSET instantiations run (a set
@@ -1744,6 +1752,7 @@ void ring_advance(KArgs& k) {
 void map_suffix(const KArgs& k, const bool mset = false) {
   const char* sfx = mset ? " set" : ((k.env_map || k.map.static_bits) ? " map" : "");
   std::strncat(g_last_kernel, sfx, sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
+  if (k.ext_stride) std::strncat(g_last_kernel, " tape", sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
 }
 
 template <int NT, bool STAGE, int NC, bool MULTI, bool RO, int TE = 0, bool MSET = false>
@@ -1898,6 +1907,7 @@ int launch_pipe2(const KArgs& k0, hipStream_t st) {
                 k.fin_obs ? " final" : "");
   if (k.log_rows) std::strncat(g_last_kernel, " log", sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
   if (k.draw_cdf) std::strncat(g_last_kernel, " draw", sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
+  if (k.ext_stride) std::strncat(g_last_kernel, " tape", sizeof(g_last_kernel) - std::strlen(g_last_kernel) - 1);
   // (recording and the final record are template flags: the instantiations without them are the code they were before;
   // the episode log and the policy draw ride on the FINAL instantiations behind uniform tests of their pointers -- no
   // flags of their own.  A map set in an n-step launch has one, MSET, on top of FINAL: the only launches that select it)
@@ -2135,6 +2145,7 @@ struct StepCall {
   const CaEpLog* log = nullptr;
   const CaPolicyDraw* draw = nullptr;  // cagpu_step_draw
   bool maps_multi = false;             // cagpu_step_ex_maps: a map / map set with n_steps > 1 or ring is admitted
+  const CaActionTape* tape = nullptr;  // cagpu_step_tape with step_stride != 0 (its `actions` is then the call's `ext`)
   // the record the entry point insists on (the older names: "traj may not be NULL" ...); cagpu_step_ex: none
   enum Need { NEED_NONE, NEED_SET, NEED_TRAJ, NEED_FIN, NEED_LOG } need = NEED_NONE;
   bool query_snapshot = false;   // cagpu_ring_snapshots: answer 1 / 0 instead of launching
@@ -2218,6 +2229,15 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
     k.log_rows = log->rows; k.log_head = log->head; k.log_cap = log->capacity;
     k.log_case_step = static_cast<int32_t>(((k.case_stride % k.n_cases) + k.n_cases) % k.n_cases);
   }
+  if (c.tape) {  // (behind every older CA_EINVAL: a call that is wrong in an older way says what it always said)
+    const CaActionTape& t = *c.tape;
+    if (!t.actions || (reinterpret_cast<uintptr_t>(t.actions) & 15u))
+      return fail(CA_EINVAL, "cagpu_step_tape: CaActionTape.actions is NULL or not 16-byte aligned%s");
+    if (t.step_stride < 0 || (t.step_stride & 1) || t.step_stride < 2 * static_cast<int64_t>(p->num_envs) * p->num_agents)
+      return fail(CA_EINVAL, "cagpu_step_tape: CaActionTape.step_stride must be 0 (one slot held) or even and >= 2 * num_envs * "
+                             "num_agents%s");
+    k.ext_stride = t.step_stride;
+  }
   k.inv_rvo_dt = 1.0 / p->rvo_dt;
   {
     static std::atomic<int> seq{0};
@@ -2273,6 +2293,22 @@ int cagpu_step_ex_maps(const CaParams* p, const CaState* s, const CaOut* o, cons
   }
   c.draw = d;
   return step_impl(p, s, o, ext_actions, ar, c, stream);
+}
+
+int cagpu_step_tape(const CaParams* p, const CaState* s, const CaOut* o, const CaActionTape* tape, const CaAutoReset* ar,
+                    const CaStepEx* x, const CaPolicyDraw* d, void* stream) {
+  // (no tape, or one slot held for all steps: cagpu_step_ex_maps itself)
+  if (!tape || tape->step_stride == 0) return cagpu_step_ex_maps(p, s, o, tape ? tape->actions : nullptr, ar, x, d, stream);
+  StepCall c;
+  c.who = "cagpu_step_ex_maps";  // (the older rules speak in that entry point's name: same code, same text)
+  c.maps_multi = true;
+  if (x) {
+    c.n_steps = x->n_steps; c.ring = x->ring != 0; c.snapshot_delta = x->snapshot_delta;
+    c.map = x->map; c.set = x->set; c.traj = x->traj; c.fin = x->fin; c.log = x->log;
+  }
+  c.draw = d;
+  c.tape = tape;
+  return step_impl(p, s, o, tape->actions, ar, c, stream);
 }
 
 int cagpu_map_draw(uint64_t seed, int32_t num_maps, const int64_t* env_ids, const int32_t* counts, int64_t n, int32_t* out,

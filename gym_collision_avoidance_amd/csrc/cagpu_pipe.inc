@@ -576,8 +576,10 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
               gx_m = px; gy_m = py;
               statics_dirty = true;
             } else if (k.ext) {
-              ext_policy_action(pol_, (k.ext + 2 * tile_base)[2 * lane], (k.ext + 2 * tile_base)[2 * lane + 1], sh_ps[lane],
-                                p.max_heading_change, spd, dh);
+              // (an action tape, cagpu_step_tape: step t of the launch reads slot t -- a kernel argument times the loop counter,
+              //  in scalar registers; ext_stride = 0: one slot held for all steps)
+              const double* const ex = k.ext + 2 * tile_base + (MULTI ? step * k.ext_stride : 0);
+              ext_policy_action(pol_, ex[2 * lane], ex[2 * lane + 1], sh_ps[lane], p.max_heading_change, spd, dh);
             }
             a0f = static_cast<float>(spd);  // float32 `all_actions`
             a1f = static_cast<float>(dh);

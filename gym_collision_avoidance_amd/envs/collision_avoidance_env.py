@@ -1285,29 +1285,77 @@ class CollisionAvoidanceEnv(Env):
         return over & ~d["in_collision"].any(dim=1) & info["final_info"]["ran_out_of_time"].any(dim=1)
 
     # ------------------------------------------------------------------ batched extras
-    def rollout(self, n_steps):
+    def _action_tape(self, n_steps, actions):
+        """rollout()'s `actions` -> float64 [n_steps, E, N, 2]: a ready array / tensor of that shape, or a sequence of
+        n_steps items, each what step() accepts (a dict by agent index, batched an [E, N, 2] array), packed by
+        _external_actions like a step's"""
+        E, N = self.num_envs, self._sim.N
+        if hasattr(actions, "shape") and len(actions.shape) == 4:
+            if tuple(actions.shape) != (n_steps, E, N, 2):
+                raise ValueError("rollout(): actions must be [n_steps, E, N, 2] = %r, got %r"
+                                 % ((n_steps, E, N, 2), tuple(actions.shape)))
+            return actions
+        if len(actions) != n_steps:
+            raise ValueError("rollout(): %d steps but %d actions" % (n_steps, len(actions)))
+        items = [self._external_actions(a) for a in actions]
+        if any(hasattr(a, "device") for a in items):
+            import torch
+            dev = self._sim.device
+            zero = torch.zeros((E, N, 2), dtype=torch.float64, device=dev)
+            return torch.stack([zero if a is None else torch.as_tensor(a, dtype=torch.float64).to(dev).reshape(E, N, 2)
+                                for a in items])
+        zero = np.zeros((E, N, 2), dtype=np.float64)
+        return np.stack([zero if a is None else np.asarray(a, dtype=np.float64).reshape(E, N, 2) for a in items])
+
+    def rollout(self, n_steps, actions=None, keep_steps=False):
         """n_steps x `step(None)` in ONE launch (`cagpu_step_ex`, CaStepEx.n_steps): the device-side form of env_utils.run_episode's
         `while not terminated: env.step(None)` loop for scenes whose policies are all internal.  Returns the last step's
         (obs, rewards, game_over, False, info); per-episode results accumulate in episode_stats() through the on-device
         auto-reset.  About 1.4x the throughput of n step() calls at 4096 x 10: a fused rollout never waits for the
-        slowest workgroup of a step."""
+        slowest workgroup of a step.
+        actions: an ACTION TAPE -- n_steps items, each what step() accepts, or a ready [n_steps, E, N, 2] array / tensor:
+        step t of the call plays actions[t] (`cagpu_step_tape`), the step of the CALL whatever episode an env is in (an env
+        that auto-resets in step t plays actions[t + 1] as the first action of its next episode).  With it agents with the
+        built-in external policies (ExternalPolicy, LearningPolicy, LearningPolicyGA3C, a policy draw whose pool holds them)
+        are admitted: open-loop evaluation of an action sequence in one launch.  Host Python policies and custom Dynamics
+        need the host between two steps and stay refused.
+        keep_steps: the outputs of EVERY step, stacked: (obs [n, E, N, W], rewards [n, E, N], game_over [n, E], False, info)
+        with info["which_agents_done"] [n, E, N] (a single env: numpy arrays [n, N, W], [n, N], [n], [n, N])."""
         if self._sim is None:
             raise RuntimeError("call reset() before rollout()")
-        if self._policy_pool is not None and any(g[0].policy.is_external for g in self._policy_pool["agents"]):
-            raise ValueError("rollout() needs every policy of the draw's pool to be internal")
-        if (any(a.policy.is_external for a in self.agents) or self._host_policies or self._host_dynamics or
-                (self._host_by_env and any(self._host_by_env)) or (self._hostdyn_by_env and any(self._hostdyn_by_env))):
-            raise ValueError("rollout() needs every policy to be internal (no external actions between the steps)")
+        n_steps = int(n_steps)
+        host_any = bool(self._host_policies or self._host_dynamics or (self._host_by_env and any(self._host_by_env)) or
+                        (self._hostdyn_by_env and any(self._hostdyn_by_env)))
+        if actions is None:
+            if self._policy_pool is not None and any(g[0].policy.is_external for g in self._policy_pool["agents"]):
+                raise ValueError("rollout() needs every policy of the draw's pool to be internal")
+            if any(a.policy.is_external for a in self.agents) or host_any:
+                raise ValueError("rollout() needs every policy to be internal (no external actions between the steps)")
+        elif host_any:
+            raise ValueError("rollout(actions=...) cannot run user Python policies or custom Dynamics: they are queried on the "
+                             "host between two steps -- use step()")
         sim = self._sim
+        tape = None if actions is None else self._action_tape(n_steps, actions)
         sim.p.dt = self.dt_nominal
-        self.episode_step_number += int(n_steps)
-        sim.rollout(int(n_steps))
+        self.episode_step_number += n_steps
+        kept = sim.rollout(n_steps, tape, keep_steps=bool(keep_steps))
         self._snap, self._obs_np, self._scan_np = None, None, None
         if Config.USE_STATIC_MAP:   # (once, on the final state: the scan kernel reads the current state)
             if self._map_lazy:
                 self._map_stale = True
             else:
                 self._map_sensors()
+        if keep_steps:
+            obs, rewards, done, over = kept
+            learning = {a.id: a.policy.is_still_learning for a in self.agents}
+            if self.num_envs > 1:
+                if self._policy_pool is not None:
+                    learning = sim.learning_mask(still_learning=True)
+                info = {"which_agents_done": done.bool(), "which_agents_learning": learning}
+                return obs, rewards, over.bool(), False, info
+            info = {"which_agents_done": done[:, 0].cpu().numpy().astype(bool), "which_agents_learning": learning}
+            return (obs[:, 0].cpu().numpy(), rewards[:, 0].double().cpu().numpy(), over[:, 0].cpu().numpy().astype(bool), False,
+                    info)
         info = {"which_agents_done": sim.done.bool() if self.num_envs > 1 else
                 {a.id: bool(d) for a, d in zip(self.agents, sim.done[0].cpu().numpy())},
                 "which_agents_learning": {a.id: a.policy.is_still_learning for a in self.agents}}

@@ -432,7 +432,8 @@ typedef struct CaStepEx {
 /* x == NULL: cagpu_step.  The rules, stated once -- every violation is CA_EINVAL with nothing launched, unless noted:
  *   n_steps  the steps fused into ONE launch (every step still writes its outputs; with ring == 0 the buffers hold the last
  *            step's).  Envs never interact, so no grid-wide sync is needed: the batched form of env_utils.py:45-52
- *            `while not terminated: env.step(None)`.  ext_actions (if any) are held constant over the n_steps.  n_steps < 1
+ *            `while not terminated: env.step(None)`.  ext_actions (if any) are held constant over the n_steps (a new action
+ *            for every step: cagpu_step_tape, below).  n_steps < 1
  *            is rejected.  The per-step inputs CaState.rvo_collab / rvo_heading_noise / ext_state belong to the ONE step that
  *            consumes them: any of them set with n_steps > 1 or ring is rejected.
  *   ring     != 0: the output pointers of `o` name slot 0 of a ring of n_steps slots and step t of the call writes slot t
@@ -483,6 +484,46 @@ int cagpu_step_ex(const CaParams *p, const CaState *s, const CaOut *o, const dou
 struct CaPolicyDraw;   /* (defined with cagpu_step_draw below) */
 int cagpu_step_ex_maps(const CaParams *p, const CaState *s, const CaOut *o, const double *ext_actions, const CaAutoReset *ar,
                        const CaStepEx *x, const struct CaPolicyDraw *draw /* may be NULL */, void *stream);
+
+/* ACTION TAPES (additive to v12): cagpu_step_ex_maps with `ext_actions` replaced by a record that may hold a NEW external
+ * action for EVERY step of a fused launch -- open-loop evaluation of an action sequence, a learner's or planner's recorded
+ * actions, in one launch instead of one per step.  The external action is read at the move of the step that consumes it (never
+ * by the policy plan of the step before), so step t reading slot t has no ordering problem. */
+typedef struct CaActionTape {
+  const double *actions;   /* device float64, slot t = [E, N, 2] in the layout of ext_actions; 16-byte aligned */
+  int64_t       step_stride; /* doubles from slot t to slot t + 1: 0 = one slot held for all steps (cagpu_step_ex's rule),
+                                otherwise even and >= 2 * E * N */
+} CaActionTape;              /* 16 bytes */
+
+/* The rules -- every violation is CA_EINVAL with nothing launched and a cagpu_last_error() text:
+ *   tape == NULL      exactly cagpu_step_ex_maps(..., ext_actions = NULL, ...).
+ *   step_stride == 0  exactly cagpu_step_ex_maps(..., ext_actions = tape->actions, ...): the same launch, the same bits, the
+ *                     same cagpu_last_kernel() string (and, as there, no check of `actions`: NULL = no external actions).
+ *   step_stride != 0  step t of the call (t = 0 .. n_steps - 1) reads actions + t * step_stride.  The index is the step of the
+ *                     LAUNCH, not the step of the episode: an env that auto-resets in step t plays slot t + 1 as the first
+ *                     action of its next episode.  Rejected: tape->actions NULL or not 16-byte aligned; step_stride negative,
+ *                     odd, or in (0, 2 * num_envs * num_agents).
+ *   everything else   every rule of cagpu_step_ex_maps holds as it does there, in that entry point's own words (a call that is
+ *                     wrong in an older way returns its code and its text): maps and sets are admitted in fused launches;
+ *                     rvo_collab / rvo_heading_noise / ext_state are rejected with n_steps > 1 or ring; the records and the
+ *                     draw are checked as there.  In the order of first-reported errors the two tape rejections stand LAST
+ *                     among the CA_EINVAL ones -- behind map and set at once, snapshot_delta without ring, the draw, the log,
+ *                     the final record, the trajectory tape, params / state / out, the map set, n_steps, the multi-step rules,
+ *                     a bad CaAutoReset and a bad CaMap -- and ahead of the ring's CA_EUNSUPPORTED (snapshot_delta without
+ *                     the pipelined n-step kernel).
+ *   who is read       only the entries of agents whose external policy is QUERIED in the step (CA_POL_EXTERNAL / _LEARNING /
+ *                     _LEARNING_GA3C, not done, present).  Entries of internal policies, of done agents and of the absent
+ *                     slots of a ragged batch are never read for effect: a NaN there changes nothing.
+ *   kernels           the kernel choice does not depend on the tape.  The n-step forms of the general and the pipelined kernel
+ *                     add t * step_stride to the slot address in scalar registers (a kernel argument times the loop counter:
+ *                     nothing joins the vector instruction stream, nothing at all where ext_actions is NULL); where a rollout
+ *                     is n launches (the large-env kernel; the general kernel beyond one resident round of workgroups) the host
+ *                     side advances the pointer per launch.  Every launch with step_stride != 0 shows " tape" at the end of
+ *                     cagpu_last_kernel(); every launch without a tape reports the string it always reported.
+ *   records           map, map set, trajectory tape, final record, episode log, policy draw and the output ring ride on a tape
+ *                     launch exactly as on any other fused launch; a ring's rewind snapshot does not cover the tape (read-only). */
+int cagpu_step_tape(const CaParams *p, const CaState *s, const CaOut *o, const CaActionTape *tape,
+                    const CaAutoReset *ar, const CaStepEx *x, const struct CaPolicyDraw *draw, void *stream);
 
 /* out[i] = the map a map-set env with global id env_ids[i] takes at its counts[i]-th auto-reset under key `seed`
  * (CaMapSet.map_seed's rule), i < n: device int64 / int32 in, device int32 out.  Lets a host say which map a logged episode
