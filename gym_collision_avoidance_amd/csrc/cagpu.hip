@@ -43,7 +43,7 @@ namespace {
 
 constexpr double kPi = 3.141592653589793;
 constexpr double kTwoPi = 2.0 * kPi;
-constexpr float kRvoEps = 0.00001f;
+#include "cagpu_lp1.inc"  // kRvoEps + the interval rule of linearProgram1 (host and device)
 
 enum { MODE_STEP = 0, MODE_RESET = 1, MODE_OBSERVE = 2 };
 

@@ -331,29 +331,75 @@ __global__ __launch_bounds__(PNT, 8) void ca_pipe_kernel(const KArgs karg) {
     const float sd = sqrtq(ok ? disc : 0.0f);
     float t_lo = -dp - sd;
     float t_hi = -dp + sd;
-    // intersect line i with the lines m < i, TWO per iteration: both lines are fetched one iteration ahead (the loop used to
-    // stand at s_waitcnt for each ds_read_b128 it had just issued) and the two divide chains are independent of each other
-    // (only the min / max of the interval is carried), so they fill each other's issue gaps
-    const auto line_at = [&](const int m) { return Lmat[((m < i) ? m : 0) * CS + ag]; };
-    float4 nx0 = line_at(0), nx1 = line_at(1);
-    for (int m = 0; m < i_hi; m += 2) {
-      const float4 l0 = nx0, l1 = nx1;
-      nx0 = line_at(m + 2);
-      nx1 = line_at(m + 3);
+    // intersect line i with the lines m < i, TWO per iteration.  Each line stays the float4 it is fetched as (ds_read_b128: one
+    // conflict-free LDS pass; the same eight dwords as two-dword reads a row apart would put four lanes on every bank) and its
+    // halves are used where they land: (x, y) = Pm and (z, w) = Dm are adjacent registers, so Pi - Pm is one packed subtract
+    // and either determinant one packed multiply against the swapped halves of the other operand + one subtract -- Pi / Di
+    // stand in one register pair each for the whole loop.  Only the two quotients are paired ACROSS the lines (den and num
+    // are computed straight into the halves of a pair), so the divide chains run packed.  (Pairing the determinants across
+    // the lines as well, as the compiler did with the scalar text, saves two multiplies and costs ten register copies per
+    // iteration to line the components up.)  The lines are fetched one iteration ahead into the OTHER of two register sets
+    // (A, B): no copy from `next` to `current` either.
+    // Rows are wave-uniform: iteration m reads rows (m, m + 1) for every lane, m + 1 <= i_hi <= N - 2; the fetch ahead is
+    // held to the last pair of rows (PAIR_HI, PAIR_HI + 1) = (N - 3, N - 2), so no read leaves rows 0 .. N - 2 of Lmat
+    // (N = 2: Lmat is one row, the "next row" is the same row; its loop never runs).
+    // What a row at or beyond an agent's neighbour count n holds is stale -- a line of an earlier step, or whatever the LDS
+    // held at the launch.  Nothing of it reaches a stored result: a line m enters t_lo / t_hi / ok only through use0 / use1
+    // (m < i), every value here is private to its lane, and `live` gates both stores -- a live item has i < n, so the lines
+    // it uses, m < i < n, were all written by this step's P2; an item with i >= n may read stale rows and is not stored.
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    constexpr int PAIR_HI = (N >= 3) ? N - 3 : 0, NEXT_ROW = (N >= 3) ? CS : 0;
+    const float4* const lcol = Lmat + ag;
+    const v2f Pi2 = v2f{Pi.x, Pi.y}, Di2 = v2f{Di.x, Di.y};
+    float eps = kRvoEps;  // one scalar register for the whole loop
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(eps));
+#endif
+    // (the empty asm behind a fetch keeps it where it is written, one iteration ahead of its use: left alone the compiler sinks
+    //  the loads to their first use, and the loop stands at s_waitcnt for every line it has just asked for)
+    const auto pair_at = [&](const int m, v4f& l0, v4f& l1) {  // m: uniform
+      const v4f* const q = reinterpret_cast<const v4f*>(lcol + (m < PAIR_HI ? m : PAIR_HI) * CS);
+      l0 = q[0];
+      l1 = q[NEXT_ROW];
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm volatile("" ::: "memory");
+#endif
+    };
+    const auto lines2 = [&](const int m, const v4f l0, const v4f l1) {
       const bool use0 = m < i, use1 = m + 1 < i;  // (i <= i_hi: the wave's first item holds its highest line)
-      const F2 Pm0 = f2(l0.x, l0.y), Dm0 = f2(l0.z, l0.w), Pm1 = f2(l1.x, l1.y), Dm1 = f2(l1.z, l1.w);
-      const float den0 = detf(Di, Dm0), den1 = detf(Di, Dm1);
-      const float num0 = detf(Dm0, Pi - Pm0), num1 = detf(Dm1, Pi - Pm1);
-      const bool par0 = fabsf(den0) <= kRvoEps, par1 = fabsf(den1) <= kRvoEps;
-      ok = ok && !(use0 && par0 && num0 < 0.0f) && !(use1 && par1 && num1 < 0.0f);
-      const float tt0 = divq(num0, par0 ? 1.0f : den0), tt1 = divq(num1, par1 ? 1.0f : den1);
-      const float h0 = (use0 && !par0 && den0 >= 0.0f) ? tt0 : INFINITY;
-      const float h1 = (use1 && !par1 && den1 >= 0.0f) ? tt1 : INFINITY;
-      const float o0 = (use0 && !par0 && den0 < 0.0f) ? tt0 : -INFINITY;
-      const float o1 = (use1 && !par1 && den1 < 0.0f) ? tt1 : -INFINITY;
-      const float hh = (h1 < h0) ? h1 : h0, oo = (o0 < o1) ? o1 : o0;
-      t_hi = (hh < t_hi) ? hh : t_hi;
-      t_lo = (t_lo < oo) ? oo : t_lo;
+      const v2f dP0 = Pi2 - l0.xy, dP1 = Pi2 - l1.xy;
+      const v2f a0 = Di2 * l0.wz, a1 = Di2 * l1.wz;  // detf(Di, Dm) = Di.x Dm.y - Di.y Dm.x
+      const v2f c0 = l0.zw * dP0.yx, c1 = l1.zw * dP1.yx;  // detf(Dm, Pi - Pm)
+      float den0 = a0.x - a0.y, den1 = a1.x - a1.y, num0 = c0.x - c0.y, num1 = c1.x - c1.y;
+#if defined(__HIP_DEVICE_COMPILE__)
+      // (four plain subtracts, each into its half of a pair: as one expression the compiler pairs them across the lines and
+      //  pays three copies per packed subtract)
+      asm volatile("" : "+v"(den0), "+v"(den1), "+v"(num0), "+v"(num1));
+#endif
+      const v2f den = v2f{den0, den1}, num = v2f{num0, num1};
+      const bool par0 = fabsf(den0) <= eps, par1 = fabsf(den1) <= eps;
+      ok = ok & !(use0 & par0 & (num0 < 0.0f)) & !(use1 & par1 & (num1 < 0.0f));
+      // divq(num, den) for both lines at once.  A parallel line's quotient (den ~ 0: anything, inf and NaN included) is never
+      // looked at: lp1_interval_pair reads tt only behind |den| > eps, so the divisor needs no `par ? 1 : den`.
+      v2f y = v2f{__builtin_amdgcn_rcpf(den0), __builtin_amdgcn_rcpf(den1)};
+      const v2f e = __builtin_elementwise_fma(-den, y, v2f(1.0f));
+      y = __builtin_elementwise_fma(e, y, y);
+      v2f q = num * y;
+      v2f r = __builtin_elementwise_fma(-den, q, num);
+      q = __builtin_elementwise_fma(r, y, q);
+      r = __builtin_elementwise_fma(-den, q, num);
+      const v2f tt = __builtin_elementwise_fma(r, y, q);
+      lp1_interval_pair(use0, use1, den0, den1, tt.x, tt.y, t_lo, t_hi, eps);
+    };
+    v4f a0_, a1_, b0_, b1_;
+    pair_at(0, a0_, a1_);
+    for (int m = 0; m < i_hi; m += 4) {
+      pair_at(m + 2, b0_, b1_);
+      lines2(m, a0_, a1_);
+      if (m + 2 >= i_hi) break;
+      pair_at(m + 4, a0_, a1_);
+      lines2(m + 2, b0_, b1_);
     }
     ok = ok && !(t_lo > t_hi);
     const float t = dotf(Di, opt - Pi);
