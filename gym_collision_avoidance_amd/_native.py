@@ -108,6 +108,11 @@ class CaActionTape(C.Structure):
     _fields_ = [("actions", _P), ("step_stride", C.c_int64)]
 
 
+class CaPoseRing(C.Structure):
+    """the pose ring of a fused launch (cagpu_tape_poses): slot t = the poses after step t; include/cagpu.h states the rule"""
+    _fields_ = [(n, _P) for n in ("pos_x", "pos_y", "heading", "radius", "step_num", "env_map")]
+
+
 class CaCaseStream(C.Structure):
     """a case stream (cagpu_stream_refill): the window table of a CaAutoReset and what keeps it ahead of the envs;
     include/cagpu.h states the rule.  side_ranges is a HOST pointer: whoever stores it keeps that array alive"""
@@ -157,7 +162,8 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_step_log", "cagpu_rollout_log", "cagpu_step_ex", "cagpu_step_draw", "cagpu_policy_draw",
            "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes", "cagpu_ga3c_query", "cagpu_ga3c_value",
            "cagpu_generate_cases_at", "cagpu_stream_refill", "cagpu_episode_metrics_carry_bytes", "cagpu_episode_metrics",
-           "cagpu_step_ex_maps", "cagpu_map_draw", "cagpu_heading_draw", "cagpu_policy_draw_at", "cagpu_step_tape")
+           "cagpu_step_ex_maps", "cagpu_map_draw", "cagpu_heading_draw", "cagpu_policy_draw_at", "cagpu_step_tape",
+           "cagpu_tape_poses", "cagpu_laserscan_slots", "cagpu_laserscan_history")
 
 _lib = None
 
@@ -232,6 +238,10 @@ def lib():
     L.cagpu_episode_metrics_carry_bytes.argtypes = [PP]
     L.cagpu_episode_metrics_carry_bytes.restype = C.c_uint64
     L.cagpu_episode_metrics.argtypes = [PP, C.POINTER(CaTraj), C.c_int32, C.POINTER(CaEpMetrics), _P]
+    L.cagpu_tape_poses.argtypes = [PP, PS, _P, C.POINTER(CaTraj), _P, C.c_int32, PA, C.POINTER(CaMapSet), C.POINTER(CaPoseRing), _P]
+    L.cagpu_laserscan_slots.argtypes = [PP, C.POINTER(CaPoseRing), C.c_int32, C.POINTER(CaMap), C.POINTER(CaMapSet),
+                                        C.POINTER(CaScan), _P, _P]
+    L.cagpu_laserscan_history.argtypes = [PP, C.POINTER(CaScan), _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]
     L.cagpu_device_faults.argtypes = [_P, C.c_int32]
     L.cagpu_device_faults_async.argtypes = [_P, _P]
     L.cagpu_workspace_bytes.argtypes = [PP]

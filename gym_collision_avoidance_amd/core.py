@@ -196,6 +196,8 @@ class BatchedSim(object):
         self._map_src = None
         # rollout(keep_steps=True) with keep_final() on: every slot's final block (final_obs [n, E, N, W], final_flags [n, E, N])
         self.kept_final = None
+        # rollout(keep_steps=True, map_sensors=True): every slot's laser scan and occupancy windows (map_slots.KeptMapSensors)
+        self.kept_map_sensors = None
 
     # ---------------------------------------------------------------- what the outside reads
     # `state` and the four outputs are those of the step last handed out: reading them goes through sync(), which rewinds a
@@ -1038,7 +1040,69 @@ class BatchedSim(object):
                              "[T, E, N, 2] with T >= n_steps = %d, got %r" % (held, n, shape))
         return self._dev(ext_actions, torch.float64), (0 if len(shape) == 3 else E * N * 2)
 
-    def rollout(self, n_steps, ext_actions=None, keep_steps=False):
+    def _map_slots_check(self, n, keep_steps):
+        """rollout(map_sensors=True): everything that can be refused is refused here, before anything is launched"""
+        if not keep_steps:
+            raise nat.CagpuError("rollout(map_sensors=True) keeps every step's sensors: it needs keep_steps=True")
+        if self._map is None:
+            raise nat.CagpuError("rollout(map_sensors=True): set_map() first")
+        if self._cstream is not None:
+            raise nat.CagpuError("rollout(map_sensors=True): a case stream (set_case_stream) is not supported -- its window of "
+                                 "cases changes under the launch, so the start poses of the episodes that begin inside it "
+                                 "cannot be restated afterwards; nothing was launched")
+        if self.N > 256:
+            raise nat.CagpuError("rollout(map_sensors=True): the laser scan supports up to 256 agents per env")
+
+    def _map_slots_budget(self, n, own_tape):
+        """the bytes the slots of this launch add -- the pose ring, the index ring and, where recording is off, the transient
+        tape -- against the tape's budget (record_trajectories' max_bytes; 1 GiB where it was never called)"""
+        from . import map_slots
+        tr = self._traj
+        budget, used = (1 << 30, 0) if tr is None else (tr["max_bytes"], tr["bytes"])
+        per = map_slots.slot_bytes(self.E, self.N, int(self._scan.num_beams), self._maps is not None)
+        need = n * (per + self.traj_step_bytes)   # (a recorded chunk is committed to the same budget by the launch itself)
+        if used + need > budget:
+            raise nat.CagpuError("rollout(map_sensors=True): %d steps need %d bytes (%d per step for the pose and index rings, "
+                                 "%d for the tape%s) and %d of max_bytes = %d are in use -- fewer steps, clear_trajectories() "
+                                 "or record_trajectories(max_bytes=...); no step was taken"
+                                 % (n, need, per, self.traj_step_bytes, " (transient)" if own_tape else "", used, budget))
+
+    def _map_slots_start(self):
+        """the few arrays of the state a launch is about to overwrite that the pose ring starts from (copies on the stream)"""
+        start = {f: self._state[f].clone() for f in ("pos_x", "pos_y", "heading", "radius", "step_num", "reset_count")}
+        if self._maps is not None:
+            start["env_map"] = self._env_map.clone()
+        return start
+
+    def _map_slots_finish(self, n, start, ct, game_over, expand_last=True):
+        """behind a fused launch: the pose ring from the launch's tape, the slot march, and (expand_last) the last slot's
+        history into `scan_hist` / `scan` -- three launches, whatever n is"""
+        from . import map_slots
+        E, N, dev, lib = self.E, self.N, self.device, self.lib
+        poses = {f: torch.empty((n, E, N), dtype=torch.int32 if f == "step_num" else torch.float64, device=dev)
+                 for f in map_slots.POSE_FIELDS}
+        if self._maps is not None:
+            poses["env_map"] = torch.empty((n, E), dtype=torch.int32, device=dev)
+        pr = nat.CaPoseRing(**{f: t.data_ptr() for f, t in poses.items()})
+        cs0 = nat.CaState(**{f: start[f].data_ptr() for f in map_slots.POSE_FIELDS + ("reset_count",)})
+        sets = None if self._maps is None else C.byref(self._maps)
+        nat.check(lib.cagpu_tape_poses(self._p_ref, C.byref(cs0), None if sets is None else start["env_map"].data_ptr(),
+                                       C.byref(ct), game_over.data_ptr(), n, self._ar_ref, sets, C.byref(pr), self._stream()))
+        idx = torch.empty((n, E, N, int(self._scan.num_beams)), dtype=torch.uint8, device=dev)
+        nat.check(lib.cagpu_laserscan_slots(self._p_ref, C.byref(pr), n, None if sets is not None else C.byref(self._map), sets,
+                                            C.byref(self._scan), idx.data_ptr(), self._stream()))
+        carried = self.scan_hist.clone()
+        kept = map_slots.KeptMapSensors(self, n, poses, idx=idx, carried=carried)
+        if not expand_last:    # (the look-ahead ring expands the slot it hands out: step_lookahead)
+            return kept
+        # the sim's own sensor state becomes the last slot's: what n single laserscan() calls would have left
+        nat.check(lib.cagpu_laserscan_history(self._p_ref, C.byref(self._scan), idx.data_ptr(), poses["step_num"].data_ptr(), n,
+                                              n - 1, 1, self.scan_hist.data_ptr(), self.scan.data_ptr(), self._stream()))
+        if self._occ is not None:
+            self.occupancy_grid()      # (stateless: the final state is the last slot's)
+        return kept
+
+    def rollout(self, n_steps, ext_actions=None, keep_steps=False, map_sensors=False):
         """n_steps steps in ONE launch (cagpu_step_ex's n_steps) -> the last step's (obs, rewards, game_over).
         ext_actions: [E, N, 2], held for all steps, or an ACTION TAPE [T, E, N, 2] (T >= n_steps): step t of the call plays
         slot t (cagpu_step_tape) -- the step of the CALL, not of the episode: an env that auto-resets in step t plays slot
@@ -1050,17 +1114,31 @@ class BatchedSim(object):
         `game_over` afterwards show the last slot.  With keep_final() on every slot has its own final block: `kept_final` =
         (final_obs [n, E, N, W], final_flags [n, E, N]), rows valid where the slot's game_over is set (None after every other
         rollout); `final_obs` / `final_flags` show the last slot's.  The trajectory tape, the episode log, maps, the policy
-        draw, the case stream and the metrics ride on either form as on rollout(n)."""
+        draw, the case stream and the metrics ride on either form as on rollout(n).
+        map_sensors (with keep_steps, after set_map): the laser scan and the occupancy windows of EVERY step as well --
+        `kept_map_sensors` (map_slots.KeptMapSensors: laserscan(t), laserscan_index(t), occupancy_grid(t), poses), from the
+        launch's trajectory tape by kernels of their own (the tape is switched on for this launch
+        alone where recording is off); `scan`, `scan_hist` and the occupancy tensors afterwards show the last slot, exactly
+        as after n x (step(), laserscan(), occupancy_grid()).  Off by default: no call or kernel changes without it."""
         self.sync()
         n = int(n_steps)
+        self.kept_map_sensors = None
+        if map_sensors:
+            self._map_slots_check(n, keep_steps)
         # (CaState.ext_state belongs to the ONE step() call that was given it: never re-applied by the steps of a rollout)
         self._cs.ext_state, self._ext_state = None, None
         e, stride = self._action_tape(ext_actions, n)
         self.kept_final = None
         if self._has_ga3c or self._rvo is not None:  # the network / the stochastic RVO draws run between steps
-            kept = []
+            kept, sens = [], []
             for t in range(n):
                 self.step(e if stride == 0 else e[t])
+                if map_sensors:   # the existing sensors, per step
+                    self.laserscan()
+                    occ = self.occupancy_grid().clone() if self._occ is not None else None
+                    sens.append((self.scan.clone(), self.scan_hist.clone(), occ) +
+                                tuple(self._state[f].clone() for f in ("pos_x", "pos_y", "heading", "radius", "step_num")) +
+                                ((self._env_map.clone(),) if self._maps is not None else ()))
                 if keep_steps:   # (torch.stack copies at the end: until then a step that writes in place must not reach them)
                     own = (lambda x: x) if self.fresh_outputs else (lambda x: x.clone())
                     kept.append(tuple(own(x) for x in (self._obs, self._rewards, self._done, self._game_over) +
@@ -1069,6 +1147,11 @@ class BatchedSim(object):
                 cols = [torch.stack(c) for c in zip(*kept)]
                 if self._fin_on:
                     self.kept_final = (cols[4], cols[5])
+                if map_sensors:
+                    from . import map_slots
+                    sc = [torch.stack(c) if c[0] is not None else None for c in zip(*sens)]
+                    poses = dict(zip(map_slots.POSE_FIELDS + ("env_map",), sc[3:]))
+                    self.kept_map_sensors = map_slots.KeptMapSensors(self, n, poses, dense=dict(scan=sc[0], hist=sc[1], occ=sc[2]))
                 return cols[0], cols[1], cols[2], cols[3]
             return self._obs, self._rewards, self._game_over
         if self.fresh_outputs and not keep_steps:
@@ -1077,7 +1160,14 @@ class BatchedSim(object):
             self._stream_refill()
         # the n steps' CaStepEx: the map or set of a single step, the tape's own chunk, the single-step final block -- it ends up holding every
         # env's most recent terminal record of the launch -- and the log, every ending in its own slot
+        if map_sensors:
+            self._map_slots_budget(n, not self._traj_on)
         chunk, ct = self._traj_chunk(n) if self._traj_on else (None, None)
+        if map_sensors:
+            if ct is None:   # recording is off: a tape for this launch alone, released with the call
+                own_tape = self._traj_alloc(n)
+                ct = nat.CaTraj(rows=own_tape[0].data_ptr(), episode=own_tape[1].data_ptr())
+            start = self._map_slots_start()
         co_ref, fin = self._co_ref, self._sx.fin
         if keep_steps:   # a ring launch without a rewind point: the look-ahead ring's layout, every slot its final block
             ring, fin_ring, cf, co, _ = self._ring_layout(n)
@@ -1096,6 +1186,8 @@ class BatchedSim(object):
             if self._met is not None:
                 self._met_process()
         self._keep = [e]   # (the tape stays alive until the next launch is queued behind this one)
+        if map_sensors:
+            self.kept_map_sensors = self._map_slots_finish(n, start, ct, ring[3])
         if keep_steps:
             # the last slot becomes the simulator's current outputs: the caller's own where the next step writes new tensors
             # anyway (fresh_outputs), a copy where it writes in place
@@ -1140,7 +1232,7 @@ class BatchedSim(object):
         and describe the step last handed out."""
         return not (self._has_ga3c or self._rvo is not None or self._variants)
 
-    def enable_lookahead(self, k, fresh=True, adaptive=False, start=None):
+    def enable_lookahead(self, k, fresh=True, adaptive=False, start=None, map_sensors=False):
         """Serve step(None) from a ring of `k` steps computed ahead of time in ONE launch (CaStepEx.ring): with every
         policy internal a step needs nothing from the host (env_utils.py:45-52 passes None until the episode is over),
         so step_lookahead() hands out slot t of the ring and launches the next k steps when it runs dry -- the fused
@@ -1159,16 +1251,24 @@ class BatchedSim(object):
         stays at one launch per step instead of alternating between rings of 1 and 2.
         What step_lookahead() returns are VIEWS of the ring's tensors (slot t of `[n, E, N, W]` ...): with fresh=True they
         are never written again and stay valid for as long as the caller holds them, but holding ONE of them keeps the
-        whole ring allocated (n slots); clone a slot that is kept long-term."""
+        whole ring allocated (n slots); clone a slot that is kept long-term.
+        map_sensors (after set_map): every refill also keeps the pose ring and the laser's index ring of its slots
+        (rollout()'s map_sensors: DESIGN.md section 3m), and every step_lookahead() expands the slot it hands out into
+        `scan` / `scan_hist` (one launch of the history kernel) and the occupancy tensors (one of the occupancy kernel),
+        without a synchronisation: the sim's sensor state is always that of the step last handed out, with the history
+        counting steps, and a rewind needs nothing extra.  Read `scan`, `scan_hist`, `occ` / `occ_bits` directly then:
+        laserscan() would measure the same state a second time."""
         self.sync()
         k = int(k)
         if k <= 0:
             self._la = None
             return
+        if map_sensors:
+            self._map_slots_check(k, True)
         cur = k if not adaptive else max(1, min(k, 8 if start is None else int(start)))
         self._la = dict(n=k, cur=cur, len=0, t=0, slots=None, fresh=bool(fresh), adaptive=bool(adaptive), ring=None,
                         snap=torch.empty_like(self._slab), fills=0, rewinds=0, in_kernel={}, prep=None, co_live=None,
-                        streak=2)
+                        streak=2, ms=bool(map_sensors), ms_kept=None)
 
     def _la_fill(self):
         la = self._la
@@ -1191,6 +1291,10 @@ class BatchedSim(object):
         k = la["cur"]
         if rec and fit < k:
             k = fit                  # (a ring is shortened to what the tape's budget still holds)
+        ms = la["ms"]
+        if ms:                       # (raises before anything changes: a case stream attached since, the byte budget)
+            self._map_slots_check(k, True)
+            self._map_slots_budget(k, not rec)
         # Everything a launch needs that does not depend on the moment of the call -- the ring's tensors, the CaOut that names
         # them, the rewind mode, the slot views handed out later -- was prepared behind the PREVIOUS launch (_la_prepare): a
         # caller who synchronises around K steps (bench.py's timed block) has the device idle until this launch is submitted
@@ -1210,9 +1314,17 @@ class BatchedSim(object):
         if rec:
             chunk, ct = self._traj_chunk(k, prep["traj"])
             prep["sx"].traj = C.addressof(ct)
+        if ms:
+            if not rec:              # recording is off: a tape for this launch alone
+                own_tape = self._traj_alloc(k)
+                ct = nat.CaTraj(rows=own_tape[0].data_ptr(), episode=own_tape[1].data_ptr())
+                prep["sx"].traj = C.addressof(ct)
+            start = self._map_slots_start()
         rc = self._launch_n(self._p_ref, self._cs_ref, prep["co_ref"], None, prep["ar_ref"], prep["sx_ref"], self._stream_handle())
         if rc != 0:
             nat.check(rc)
+        if ms:
+            la["ms_kept"] = self._map_slots_finish(k, start, ct, prep["ring"][3], expand_last=False)
         if chunk is not None:
             la["traj"] = self._traj_commit(chunk)
         la["slots"] = prep["slots"]
@@ -1286,6 +1398,8 @@ class BatchedSim(object):
             self._la_fill()
             t = 0
         la["t"] = t + 1
+        if la["ms"]:
+            la["ms_kept"].expand_into_sim(t)
         return la["slots"][t]
 
     def lookahead_final(self):

@@ -766,6 +766,7 @@ __device__ __forceinline__ void reset_lane(Lane& r, const double* c, const bool 
 
 #include "cagpu_rules.inc"
 #include "cagpu_replay.inc"
+#include "cagpu_poses.inc"
 
 // MSET: the n-step form (MULTI) also runs the map-set code of the single-step form -- the per-env grid of A3, the map draw
 // of an auto-reset.  A template flag that only a set launch with n_steps > 1 selects (launch_main4): every other
@@ -2448,12 +2449,13 @@ int cagpu_rollout_log(const CaParams* p, const CaState* s, const CaOut* o, const
   return step_impl(p, s, o, ext_actions, ar, c, stream);
 }
 
+// idx_out: the slot march (cagpu_laserscan_slots) -- scan_kernel<true> writes the new index rows there and no history
 static int laserscan_impl(const CaParams* p, const CaState* s, const CaMap* map, const CaScan* scan, void* stream,
-                          const CaMapSet* set = nullptr) {
+                          const CaMapSet* set = nullptr, uint8_t* idx_out = nullptr) {
   if (!p || !s || !map || !scan) return fail(CA_EINVAL, "cagpu_laserscan: NULL argument%s");
   if (p->num_envs < 1 || p->num_agents < 1 || p->num_agents > 256) return fail(CA_EINVAL, "cagpu_laserscan: bad sizes%s");
   if (map->rows < 1 || map->cols < 1 || !(map->cell > 0.0)) return fail(CA_EINVAL, "cagpu_laserscan: bad CaMap%s");
-  if (!scan->hist || !scan->out || scan->num_beams < 2 || scan->num_to_store < 1 || scan->num_ranges < 1 ||
+  if ((!idx_out && (!scan->hist || !scan->out)) || scan->num_beams < 2 || scan->num_to_store < 1 || scan->num_ranges < 1 ||
       scan->num_ranges > 255)
     return fail(CA_EINVAL, "cagpu_laserscan: bad CaScan%s");
   if (!s->pos_x || !s->pos_y || !s->heading || !s->radius || !s->step_num) return fail(CA_EINVAL, "cagpu_laserscan: NULL state pointer%s");
@@ -2466,16 +2468,18 @@ static int laserscan_impl(const CaParams* p, const CaState* s, const CaMap* map,
   std::memset(&k, 0, sizeof(k));
   k.p = *p; k.s = *s; k.m = *map; k.sc = *scan;
   if (set) { k.env_map = set->env_map; k.num_maps = set->num_maps; }
+  if (idx_out) { k.sc.hist = idx_out; k.sc.out = nullptr; }  // (scan_kernel<true>: the index rows go where the history would)
   const int N = p->num_agents;
   const size_t total = align16(scan_grid_words(map->rows, map->cols) * 4) + static_cast<size_t>(N) * (4 * 8 + 2 * 8 + 3 * 4 + 2 * 8 + 2 * 8 + 3 * 4 + 4 * 4) +
                        static_cast<size_t>(scan->num_beams) * 16 + 256 * 4 + 32 + static_cast<size_t>(HIST_AG) * SCAN_NT;
   if (total > 160 * 1024) return fail(CA_EUNSUPPORTED, "cagpu_laserscan: map too large for the LDS bitmap%s");
+  const auto kernel = idx_out ? &scan_kernel<true> : &scan_kernel<false>;
   if (total > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_kernel),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(total));
     if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: hipFuncSetAttribute: %s", hipGetErrorString(e));
   }
-  hipLaunchKernelGGL(scan_kernel, dim3(static_cast<unsigned>(p->num_envs)), dim3(SCAN_NT), total,
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(p->num_envs)), dim3(SCAN_NT), total,
                      static_cast<hipStream_t>(stream), k);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
@@ -3072,6 +3076,117 @@ int cagpu_orca(int32_t num_envs, int32_t num_agents, const float* pos, const flo
     case 128: return launch_orca<128>(k, st);
     default: return launch_orca<256>(k, st);
   }
+}
+
+// ---- map sensors for every step of a fused launch (csrc/cagpu_poses.inc)
+static bool bad_ptr(const void* q, uintptr_t mask) { return !q || (reinterpret_cast<uintptr_t>(q) & mask); }
+
+static int check_pose_ring(const CaPoseRing* r, const bool need_map, const char* who) {
+  if (!r) return fail(CA_EINVAL, "%s: NULL CaPoseRing", who);
+  if (bad_ptr(r->pos_x, 15) || bad_ptr(r->pos_y, 15) || bad_ptr(r->heading, 15) || bad_ptr(r->radius, 15) ||
+      bad_ptr(r->step_num, 15))
+    return fail(CA_EINVAL, "%s: a CaPoseRing array is NULL or not 16-byte aligned", who);
+  if (need_map ? bad_ptr(r->env_map, 3) : (reinterpret_cast<uintptr_t>(r->env_map) & 3) != 0)
+    return fail(CA_EINVAL, "%s: CaPoseRing.env_map NULL with a map set, or not 4-byte aligned", who);
+  return CA_OK;
+}
+
+int cagpu_tape_poses(const CaParams* p, const CaState* start, const int32_t* start_env_map, const CaTraj* traj,
+                     const uint8_t* game_over, int32_t n_steps, const CaAutoReset* ar, const CaMapSet* set,
+                     const CaPoseRing* ring, void* stream) {
+  const char* who = "cagpu_tape_poses";
+  if (!p || !start || !traj || !game_over || !ring) return fail(CA_EINVAL, "%s: NULL argument", who);
+  if (p->num_envs < 1 || p->num_agents < 1 || p->num_agents > big::NT_MAX) return fail(CA_EINVAL, "%s: bad sizes", who);
+  if (n_steps < 0) return fail(CA_EINVAL, "%s: n_steps < 0", who);
+  if (!start->pos_x || !start->pos_y || !start->heading || !start->radius || !start->step_num || !start->reset_count)
+    return fail(CA_EINVAL, "%s: NULL state pointer", who);
+  if (bad_ptr(traj->rows, 15)) return fail(CA_EINVAL, "%s: traj->rows NULL or not 16-byte aligned", who);
+  if (set) {
+    if (set->num_maps < 1) return fail(CA_EINVAL, "%s: CaMapSet.num_maps < 1", who);
+    if (bad_ptr(start_env_map, 3)) return fail(CA_EINVAL, "%s: start_env_map NULL or not 4-byte aligned with a map set", who);
+  }
+  if (ar && (!ar->table || ar->n_cases < 1)) return fail(CA_EINVAL, "%s: bad CaAutoReset", who);
+  const int rc = check_pose_ring(ring, set != nullptr, who);
+  if (rc) return rc;
+  if (n_steps == 0) return CA_OK;
+  PoseArgs k;
+  std::memset(&k, 0, sizeof(k));
+  k.p = *p;
+  k.pos_x = start->pos_x; k.pos_y = start->pos_y; k.heading = start->heading; k.radius = start->radius;
+  k.step_num = start->step_num; k.reset_count = start->reset_count;
+  k.env_map_in = set ? start_env_map : nullptr;
+  k.rows = traj->rows; k.game_over = game_over; k.n_steps = n_steps;
+  if (ar) {
+    k.table = ar->table; k.n_cases = ar->n_cases; k.env_id_offset = ar->env_id_offset; k.case_stride = ar->case_stride;
+    k.heading_seed = ar->heading_seed;
+    if (set) { k.map_seed = set->map_seed; k.num_maps = set->num_maps; }
+  }
+  k.o_px = ring->pos_x; k.o_py = ring->pos_y; k.o_hd = ring->heading; k.o_rad = ring->radius;
+  k.o_step = ring->step_num; k.o_map = set ? ring->env_map : nullptr;
+  const long EN = static_cast<long>(p->num_envs) * p->num_agents;
+  hipLaunchKernelGGL(poses_kernel, dim3(static_cast<unsigned>((EN + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), k);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
+}
+
+int cagpu_laserscan_slots(const CaParams* p, const CaPoseRing* ring, int32_t n_steps, const CaMap* map, const CaMapSet* set,
+                          const CaScan* scan, uint8_t* idx, void* stream) {
+  const char* who = "cagpu_laserscan_slots";
+  if (!p || !ring || !scan || (!map && !set)) return fail(CA_EINVAL, "%s: NULL argument", who);
+  if (map && set) return fail(CA_EINVAL, "%s: map and set at once", who);
+  if (p->num_envs < 1 || p->num_agents < 1) return fail(CA_EINVAL, "%s: bad sizes", who);
+  if (n_steps < 0) return fail(CA_EINVAL, "%s: n_steps < 0", who);
+  if (static_cast<long>(n_steps) * p->num_envs > 0x7FFFFFFFL) return fail(CA_EUNSUPPORTED, "%s: more than 2^31 - 1 (slot, env) pairs", who);
+  if (bad_ptr(idx, 15)) return fail(CA_EINVAL, "%s: idx NULL or not 16-byte aligned", who);
+  if (set && (!set->map.static_bits || set->num_maps < 1)) return fail(CA_EINVAL, "%s: bad CaMapSet", who);
+  const int rc = check_pose_ring(ring, set != nullptr, who);
+  if (rc) return rc;
+  if (n_steps == 0) return CA_OK;
+  CaParams pp = *p;
+  pp.num_envs = p->num_envs * n_steps;  // the ring is [n, E, N]: n x E envs of N agents
+  CaState s;
+  std::memset(&s, 0, sizeof(s));
+  s.pos_x = ring->pos_x; s.pos_y = ring->pos_y; s.heading = ring->heading; s.radius = ring->radius; s.step_num = ring->step_num;
+  if (set) {
+    CaMapSet ms = *set;
+    ms.env_map = ring->env_map;
+    return laserscan_impl(&pp, &s, &ms.map, scan, stream, &ms, idx);
+  }
+  return laserscan_impl(&pp, &s, map, scan, stream, nullptr, idx);
+}
+
+int cagpu_laserscan_history(const CaParams* p, const CaScan* scan, const uint8_t* idx, const int32_t* step_num, int32_t n_steps,
+                            int32_t first, int32_t count, uint8_t* hist_out, float* out, void* stream) {
+  const char* who = "cagpu_laserscan_history";
+  if (!p || !scan) return fail(CA_EINVAL, "%s: NULL argument", who);
+  if (p->num_envs < 1 || p->num_agents < 1) return fail(CA_EINVAL, "%s: bad sizes", who);
+  if (scan->num_beams < 2 || scan->num_to_store < 1 || scan->num_ranges < 1 || scan->num_ranges > 255)
+    return fail(CA_EINVAL, "%s: bad CaScan", who);
+  if (n_steps < 1 || first < 0 || count < 0 || first > n_steps - count)
+    return fail(CA_EINVAL, "%s: n_steps < 1 or [first, first + count) outside the n_steps slots", who);
+  if (bad_ptr(idx, 15) || bad_ptr(step_num, 15) || bad_ptr(scan->hist, 15))
+    return fail(CA_EINVAL, "%s: idx, step_num or CaScan.hist NULL or not 16-byte aligned", who);
+  if ((!hist_out && !out) || ((reinterpret_cast<uintptr_t>(hist_out) | reinterpret_cast<uintptr_t>(out)) & 15))
+    return fail(CA_EINVAL, "%s: both outputs NULL, or an output not 16-byte aligned", who);
+  if (hist_out == scan->hist && count != 1)
+    return fail(CA_EINVAL, "%s: only a single slot may be expanded in place (hist_out == CaScan.hist)", who);
+  if (count == 0) return CA_OK;
+  ScanHistArgs k;
+  std::memset(&k, 0, sizeof(k));
+  k.idx = idx; k.step_num = step_num; k.carried = scan->hist; k.o_hist = hist_out; k.o_out = out;
+  k.EN = static_cast<long>(p->num_envs) * p->num_agents;
+  k.first = first; k.count = count; k.B = scan->num_beams; k.H = scan->num_to_store;
+  k.range_res = scan->range_res; k.max_range = scan->max_range;
+  const bool vec = (k.B & 3) == 0;
+  const long threads = k.EN * (vec ? k.B / 4 : k.B) * count;
+  if ((threads + 255) / 256 > 0x7FFFFFFFL) return fail(CA_EUNSUPPORTED, "%s: too many (slot, agent, beam) items for one launch", who);
+  const dim3 grid(static_cast<unsigned>((threads + 255) / 256));
+  if (vec) hipLaunchKernelGGL(scan_hist_kernel<4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), k);
+  else hipLaunchKernelGGL(scan_hist_kernel<1>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), k);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CA_ELAUNCH, "cagpu: kernel launch failed: %s", hipGetErrorString(e));
+  return CA_OK;
 }
 
 }  // extern "C"

@@ -86,6 +86,11 @@ __host__ __device__ inline size_t scan_grid_words(int rows, int cols) {  // LDS 
 // (profiles/r04_kernel_geometry.md section 3).  What did pay at the end of the round, all in the loop below: the border test on
 // coordinates biased by its margin, the hit bookkeeping skipped for groups in which no beam of the wave hit anything, the
 // per-agent part of a beam's set-up computed once per agent, the clip in float32, the range table: 1436 -> 1162 us.
+// SLOTS: the slot march's form (cagpu_laserscan_slots: the (slot, env) pairs of a pose ring as n x E envs) -- the same
+// staging, rasterisation and march, but the range indices go out as ONE new row per agent, uint8 [E, N, B] at sc.hist
+// (sc.out is not used), instead of into the rolled history.  A template flag: scan_kernel<false> is the code, and takes the
+// arguments, that scan_kernel was and took before the flag existed.
+template <bool SLOTS>
 __global__ __launch_bounds__(SCAN_NT) void scan_kernel(const ScanArgs k) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int N = k.p.num_agents;
@@ -230,7 +235,7 @@ __global__ __launch_bounds__(SCAN_NT) void scan_kernel(const ScanArgs k) {
   // one dword of range indices per row loaded / stored, one float4 of ranges per row stored -- instead of a byte load, a byte
   // store and a 4-byte store per beam and row (64-byte and 256-byte wave transactions; ~80 of the ~570 wave-instructions
   // per (agent, 64 beams)).  Other beam counts keep the per-beam form.
-  const bool vec_hist = (B == SCAN_NT) && ((reinterpret_cast<uintptr_t>(k.sc.hist) | reinterpret_cast<uintptr_t>(k.sc.out)) & 15) == 0;
+  const bool vec_hist = (B == SCAN_NT) && ((reinterpret_cast<uintptr_t>(k.sc.hist) | (SLOTS ? 0 : reinterpret_cast<uintptr_t>(k.sc.out))) & 15) == 0;
   for (int t0 = 0; t0 < N * B; t0 += SCAN_NT) {
     const int t = t0 + tid;
     const bool in_range = t < N * B;
@@ -370,6 +375,10 @@ __global__ __launch_bounds__(SCAN_NT) void scan_kernel(const ScanArgs k) {
       if (slot == HIST_AG - 1 || last_round) {
         __syncthreads();
         const int n_ag = slot + 1, first_ag = a0 - slot;
+        if constexpr (SLOTS) {  // the staged agents' rows are contiguous: four beams per store, nothing else
+          uint32_t* dst = reinterpret_cast<uint32_t*>(k.sc.hist + (e * N + first_ag) * B);
+          for (int g = tid; g < n_ag * (B / 4); g += SCAN_NT) dst[g] = idx_st[g];
+        } else
         for (int g = tid; g < n_ag * (B / 4); g += SCAN_NT) {
           const int sa = g / (B / 4), q4 = g - sa * (B / 4), ag = first_ag + sa;
           const long ii = e * N + ag;
@@ -399,6 +408,10 @@ __global__ __launch_bounds__(SCAN_NT) void scan_kernel(const ScanArgs k) {
       continue;
     }
     if (!in_range) continue;
+    if constexpr (SLOTS) {
+      k.sc.hist[(e * N + a) * B + b] = static_cast<uint8_t>(idx);
+      continue;
+    }
     const long i = e * N + a;
     uint8_t* hist = k.sc.hist + (i * H) * B + b;
     float* out = k.sc.out + (i * H) * B + b;

@@ -126,6 +126,7 @@ class CollisionAvoidanceEnv(Env):
         self._has_map_index = False   # ... `map_index`, the device int32 [E] map of every env, exists (a property)
         self._map_lazy = False    # sense_map_on_demand(): map sensors when asked for, not after every step
         self._map_stale = False   # ... and a step came since they were last computed
+        self._map_ring = False    # sense_map_in_ring(): the ring keeps the map sensors of every slot it computes
         self.episode_step_number = None
         self.episode_number = 0
         self.plot_save_dir = None
@@ -306,7 +307,10 @@ class CollisionAvoidanceEnv(Env):
                 self._la_dt_ok = True
             self.episode_step_number += 1
             self._snap = self._obs_np = self._scan_np = None
-            self._map_stale = True   # (a ring runs map batches only with sense_map_on_demand)
+            # (a ring runs map batches only with sense_map_on_demand, which computes the sensors when asked, or with
+            #  sense_map_in_ring, whose hand-out has already made them those of this step)
+            self._map_stale = not self._map_ring
+            self._occ_np = None
             obs, rewards, done, over = sim.step_lookahead()
             info = {"which_agents_done": done, "which_agents_learning": self._learning_info}
             if sim._fin_on:
@@ -690,8 +694,8 @@ class CollisionAvoidanceEnv(Env):
         self._la_but_map = bool(self._policy_pool is None and   # (a draw: the learning mask of every step is read from the state)
                                 E > 1 and ring > 0 and not nets and not host_any and
                                 not any(a.policy.is_external for g in groups for a in g) and sim.lookahead_ok())
-        self._la_on = self._la_but_map and (not Config.USE_STATIC_MAP or self._map_lazy)
-        sim.enable_lookahead(ring if self._la_on else 0, fresh=not self.zero_copy, adaptive=True)
+        self._la_on = self._la_but_map and (not Config.USE_STATIC_MAP or self._map_lazy or self._map_ring)
+        self._enable_ring(sim)
         self._la_dt_ok = sim.p.dt == self.dt_nominal
         if self._la_on:
             self._learning_info = {a.id: a.policy.is_still_learning for a in self.agents}
@@ -709,6 +713,7 @@ class CollisionAvoidanceEnv(Env):
             self.map = maps[int(idx[0])]
             self._has_map_index = True
             self._map_sensors(groups)
+            self._enable_ring(sim)    # (sense_map_in_ring: the ring's sensor slots need the map just attached)
         elif Config.USE_STATIC_MAP:  # collision_avoidance_env.py:273-274, :378-392: Map(16 m, 16 m, 0.1 m)
             sm = self.static_map_filename
             if isinstance(sm, list) and sm and isinstance(sm[0], str):
@@ -717,6 +722,7 @@ class CollisionAvoidanceEnv(Env):
             sim.set_map(self.map.static_map if self.map.static_map.any() else None, num_beams=Config.LASERSCAN_LENGTH,
                         num_to_store=Config.LASERSCAN_NUM_PAST)
             self._map_sensors(groups)
+            self._enable_ring(sim)
         if Config.STORE_HISTORY and E == 1:
             self._record_history(initial=True)
 
@@ -846,10 +852,37 @@ class CollisionAvoidanceEnv(Env):
         sim.sync()
         if not on:
             self._map_fresh()
-        self._la_on = self._la_but_map and on
-        sim.enable_lookahead(self._ring_len(sim) if self._la_on else 0, fresh=not self.zero_copy, adaptive=True)
+        self._la_on = self._la_but_map and (on or self._map_ring)
+        self._enable_ring(sim)
         if self._la_on:
             self._learning_info = {a.id: a.policy.is_still_learning for a in self.agents}
+
+    def sense_map_in_ring(self, on=True):
+        """Opt-in for Config.USE_STATIC_MAP batches whose policies are all internal: step(None) is served from the
+        look-ahead ring AND `env.laserscan`, `env.occupancy_grid` and the observation dict show the true sensors of every
+        step -- the scan history counts steps, not requests (sense_map_on_demand's does).  A refill computes the laser
+        index rows of all its slots behind the step launch (core.BatchedSim.enable_lookahead(map_sensors=True)) and every
+        step(None) expands the slot it hands out, without a synchronisation.  rollout(n, actions=..., keep_steps=True) then
+        returns every step's sensors too: info["laserscan"] [n, E, N, LASERSCAN_NUM_PAST, LASERSCAN_LENGTH] and, where an
+        agent lists the OccupancyGridSensor, info["occupancy_grid"] [n, E, N, H, W].  Off by default."""
+        on = bool(on)
+        if on == self._map_ring:
+            return
+        self._map_ring = on
+        if self._sim is None or not Config.USE_STATIC_MAP:
+            return
+        sim = self._sim
+        sim.sync()
+        self._map_fresh()
+        self._la_on = self._la_but_map and (on or self._map_lazy)
+        self._enable_ring(sim)
+        if self._la_on:
+            self._learning_info = {a.id: a.policy.is_still_learning for a in self.agents}
+
+    def _enable_ring(self, sim):
+        """the look-ahead ring as the switches stand: off, plain, or keeping the map sensors of its slots"""
+        ms = bool(self._la_on and self._map_ring and Config.USE_STATIC_MAP and sim._map is not None)
+        sim.enable_lookahead(self._ring_len(sim) if self._la_on else 0, fresh=not self.zero_copy, adaptive=True, map_sensors=ms)
 
     def _map_sensors(self, groups=None):
         """the map sensors of the current state: the laser scan, and the OccupancyGridSensor windows where some agent of
@@ -1267,13 +1300,17 @@ class CollisionAvoidanceEnv(Env):
         if self.lookahead is not None:
             return self.lookahead
         slot_bytes = self.num_envs * sim.N * (4 * sim.W + 5) + self.num_envs + (sim.final_step_bytes if sim._fin_on else 0)
+        if self._map_ring and Config.USE_STATIC_MAP:   # the pose ring, the laser's index ring and the launch's tape
+            from gym_collision_avoidance_amd import map_slots
+            slot_bytes += map_slots.slot_bytes(self.num_envs, sim.N, Config.LASERSCAN_LENGTH, self._map_set is not None)
+            slot_bytes += sim.traj_step_bytes
         return int(min(self.LOOKAHEAD_MAX, max(8, self.LOOKAHEAD_BYTES // slot_bytes)))
 
     def _resize_ring(self):
         """the default ring length follows the bytes of a slot: recomputed when the final record is toggled"""
         if not self._la_on or self.lookahead is not None:
             return
-        self._sim.enable_lookahead(self._ring_len(self._sim), fresh=not self.zero_copy, adaptive=True)
+        self._enable_ring(self._sim)
 
     def _final_items(self, info, over, final_obs, final_flags):
         """adds "final_observation" / "final_info" to `info` -> truncated [E] (a few elementwise device ops, no sync)"""
@@ -1338,9 +1375,13 @@ class CollisionAvoidanceEnv(Env):
         tape = None if actions is None else self._action_tape(n_steps, actions)
         sim.p.dt = self.dt_nominal
         self.episode_step_number += n_steps
-        kept = sim.rollout(n_steps, tape, keep_steps=bool(keep_steps))
+        # sense_map_in_ring: every step's sensors (batched)
+        slots = bool(keep_steps and self._map_ring and Config.USE_STATIC_MAP and self.num_envs > 1)
+        kept = sim.rollout(n_steps, tape, keep_steps=bool(keep_steps), map_sensors=slots)
         self._snap, self._obs_np, self._scan_np = None, None, None
-        if Config.USE_STATIC_MAP:   # (once, on the final state: the scan kernel reads the current state)
+        if slots:                   # (the sim's sensor tensors already show the last slot)
+            self._occ_np, self._map_stale = None, False
+        elif Config.USE_STATIC_MAP:   # (once, on the final state: the scan kernel reads the current state)
             if self._map_lazy:
                 self._map_stale = True
             else:
@@ -1352,6 +1393,10 @@ class CollisionAvoidanceEnv(Env):
                 if self._policy_pool is not None:
                     learning = sim.learning_mask(still_learning=True)
                 info = {"which_agents_done": done.bool(), "which_agents_learning": learning}
+                if slots:
+                    info["laserscan"] = sim.kept_map_sensors.laserscan()
+                    if sim.occ is not None:
+                        info["occupancy_grid"] = sim.kept_map_sensors.occupancy_grid()
                 return obs, rewards, over.bool(), False, info
             info = {"which_agents_done": done[:, 0].cpu().numpy().astype(bool), "which_agents_learning": learning}
             return (obs[:, 0].cpu().numpy(), rewards[:, 0].double().cpu().numpy(), over[:, 0].cpu().numpy().astype(bool), False,

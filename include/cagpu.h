@@ -947,6 +947,64 @@ int cagpu_debug_copy8(int64_t n, const double *src, double *dst, void *stream);
 uint64_t cagpu_episode_metrics_carry_bytes(const CaParams *p);   /* 0 for bad sizes; host-only call */
 int cagpu_episode_metrics(const CaParams *p, const CaTraj *traj, int32_t n_steps, const CaEpMetrics *m, void *stream);
 
+/* MAP SENSORS FOR EVERY STEP OF A FUSED LAUNCH (additive to v12).  cagpu_laserscan and
+ * cagpu_occupancy_grid read the CURRENT state, which after an n-step launch is the final one.  The three calls below give
+ * the sensors of every step of such a launch from what it recorded, with kernels of their own -- no step kernel knows
+ * about them (tests/pose_tape_ref.py is the NumPy statement of the two rules).
+ *
+ * POSE RING: structure-of-arrays, slot t = the poses after step t of the launch; slot t of every array, taken at its
+ * pointer offset, is a CaState view that cagpu_laserscan / cagpu_occupancy_grid accept, and the whole ring is one batch of
+ * n_steps x num_envs envs (env_map: its map-set indices). */
+typedef struct CaPoseRing {
+  double  *pos_x, *pos_y, *heading, *radius; /* device [n_steps, E, N], 16-byte aligned */
+  int32_t *step_num;                         /* device [n_steps, E, N], 16-byte aligned */
+  int32_t *env_map;                          /* device [n_steps, E]; NULL without a map set */
+} CaPoseRing;                                /* 48 bytes */
+
+/* The pose ring of one launch of n_steps steps, restated from
+ *   start          the state as the launch FOUND it (pos_x, pos_y, heading, radius, step_num [E,N] and reset_count [E] are
+ *                  read: the caller copies them on the stream ahead of the launch), start_env_map [E] with a set;
+ *   traj           the launch's tape chunk (rows [n_steps, E, N, 12]; episode is not read);
+ *   game_over      the launch's game_over ring, uint8 [n_steps, E] (CaOut.game_over of a ring launch);
+ *   ar, set        the CaAutoReset and CaMapSet the launch ran with (either may be NULL; of the set only num_maps and
+ *                  map_seed are read).
+ * THE POSE RULE, per agent slot with t ascending:
+ *   1. a row whose column 11 is >= 0 replaces position (columns 1, 2) and heading (column 10); step_num = column 11 + 1;
+ *   2. any other row keeps the carried pose (nothing else of such a row is read);
+ *   3. where game_over[t, e] is set and ar is given, the pose becomes the START pose of the env's next episode -- the
+ *      table row of the auto-reset's case, the heading towards the goal or CaAutoReset.heading_seed's draw, zeros for an
+ *      absent slot of a ragged table (CaParams.ragged) -- and step_num 0;
+ *   4. with set->map_seed != 0 the slot's env_map entry is the map drawn at that auto-reset (CaMapSet.map_seed).
+ * Steps 3 and 4 call the device functions the step kernels call.  A case stream's window (CaCaseStream) changes under
+ * the launch that follows a refill: the caller must not use this call with one.  CA_EINVAL, nothing launched: a NULL
+ * argument (ar / set / start_env_map without a set excepted), bad sizes, n_steps < 0, a NULL state pointer, traj->rows or
+ * a ring array NULL or not 16-byte aligned, ring->env_map NULL with a set, a CaAutoReset without a table.  n_steps == 0
+ * does nothing.  cagpu_last_kernel() is left alone by all three calls. */
+int cagpu_tape_poses(const CaParams *p, const CaState *start, const int32_t *start_env_map, const CaTraj *traj,
+                     const uint8_t *game_over, int32_t n_steps, const CaAutoReset *ar, const CaMapSet *set,
+                     const CaPoseRing *ring, void *stream);
+
+/* The laser scan's march over every slot of a pose ring: cagpu_laserscan's staging, rasterisation and march (the same
+ * device code, csrc/cagpu_scan.inc) with one workgroup per (slot, env), against `map` or the slot's own map of `set`
+ * (exactly one of the two; ring->env_map is used, set->env_map is not read).  Writes only the NEW range-index row of
+ * every agent, idx uint8 [n_steps, E, N, num_beams] (255 = nothing hit): no history is read or written and scan->hist /
+ * scan->out may be NULL.  CA_EINVAL / CA_EUNSUPPORTED as cagpu_laserscan (num_agents <= 256), and CA_EINVAL for map and
+ * set at once, idx NULL or not 16-byte aligned, a bad ring; n_steps x num_envs above 2^31 - 1 is CA_EUNSUPPORTED. */
+int cagpu_laserscan_slots(const CaParams *p, const CaPoseRing *ring, int32_t n_steps, const CaMap *map, const CaMapSet *set,
+                          const CaScan *scan, uint8_t *idx, void *stream);
+
+/* The LaserScanSensor history of slots first .. first + count - 1 of a launch of n_steps slots.  THE HISTORY RULE
+ * (LaserScanSensor.py:84-88): row j of slot t is the index row of slot max(t - j, s), s the latest slot <= t whose
+ * step_num (of the pose ring) is 0 -- the first measurement of an episode fills every row --, and a slot before the
+ * launch is the history the launch found: slot -1 - r = row r of scan->hist (read only, unless written in place).
+ * Outputs, either may be NULL (not both), 16-byte aligned: hist_out uint8 and out float32 metres, both
+ * [count, E, N, num_to_store, num_beams].  In place: with count == 1, hist_out == scan->hist (and out == scan->out)
+ * leaves exactly the state n_steps single cagpu_laserscan calls leave when slot n_steps - 1 is expanded.  CA_EINVAL,
+ * nothing launched: NULL p / scan / idx / step_num / scan->hist, misaligned pointers, a bad CaScan, a slot range outside
+ * the launch, hist_out == scan->hist with count != 1.  count == 0 does nothing. */
+int cagpu_laserscan_history(const CaParams *p, const CaScan *scan, const uint8_t *idx, const int32_t *step_num, int32_t n_steps,
+                            int32_t first, int32_t count, uint8_t *hist_out, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
