@@ -181,7 +181,7 @@ struct Geo {
 // stores the terminal flag words in A4, the S-pair waves save the terminal rows in front of their reset-observation copy.
 // A template flag for the same reason.
 // MSET: the n-step form (MULTI) also runs the map-set code of the single-step form -- the per-env grid of A3, the map draw
-// of an auto-reset.  Only a set launch with n_steps > 1 selects it (launch_pipe2, always together with FINAL).  A flag of its
+// of an auto-reset.  Only a set launch with n_steps > 1 selects it (pipe_kernel in cagpu_launch.inc, always together with FINAL).  A flag of its
 // own and not a uniform test inside the FINAL instantiations: behind a test the set code cost those kernels -- which
 // map-less launches with the final record, the episode log or the policy draw run -- their register budget (scratch
 // spills inside the step loop at N = 10); with the flag every instantiation without it is the code it was.

@@ -45,7 +45,7 @@ Classes (VARIANTS lists their variants):
      NOT built, because no finite operands give them: an agent standing ON its goal (RVOPolicy.py:67 divides by the distance:
      NaN), and dpy = -0 (dpy = float32 position - float64 position of equal values: x - x = +0 whatever the signs).
 
-pipelined_eligible() restates cagpu.hip pipe_eligible() for these scenes: every class runs on every path."""
+pipelined_eligible() restates cagpu_launch.inc pipe_eligible() for these scenes: every class runs on every path."""
 import ctypes as C
 import math
 
@@ -103,7 +103,7 @@ def bits(x):
 
 
 def pipelined_eligible(cls, variant):
-    """csrc/cagpu.hip pipe_eligible(): no per-step RVO inputs and no ext_state (these scenes have none), an instantiated agent
+    """csrc/cagpu_launch.inc pipe_eligible(): no per-step RVO inputs and no ext_state (these scenes have none), an instantiated agent
     count (orca_scenes.PIPE_TILE), closest_first sorting (every scene here); external actions, the dynamics and the policies
     do not matter to it"""
     return True

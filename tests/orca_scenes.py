@@ -44,7 +44,7 @@ PIPE_TILE = {2: 32, 3: 21, 4: 16, 5: 12, 6: 10, 8: 8, 10: 4}
 
 
 def tiled_envs(N):
-    """envs per workgroup of ca_kernel at a small batch (launch_any, csrc/cagpu.hip)"""
+    """envs per workgroup of ca_kernel at a small batch (launch_any, csrc/cagpu_launch.inc)"""
     return 4 if N == 10 else 64 // N
 
 

@@ -51,7 +51,7 @@ Classes (VARIANTS lists their variants):
      absent.  Variants: sort mode x max_obs "below" (cuts a tied group of the host's list: one kept, one dropped), "equal"
      (N - 1), "above" (N + 1).
 
-Which launch path runs what: pipelined_eligible() restates cagpu.hip pipe_eligible() for these scenes -- the pipelined kernel
+Which launch path runs what: pipelined_eligible() restates cagpu_launch.inc pipe_eligible() for these scenes -- the pipelined kernel
 takes external actions and a static map, but only closest_first sorting, so the other two sort modes of class s run on the other
 paths only.  MIN_AGENTS is the rule by which a class is skipped at a shape too small for it."""
 import math
@@ -93,7 +93,7 @@ LABELS = {
 
 
 def pipelined_eligible(cls, variant):
-    """csrc/cagpu.hip pipe_eligible(): no per-step RVO inputs and no ext_state (these scenes have none), an instantiated agent
+    """csrc/cagpu_launch.inc pipe_eligible(): no per-step RVO inputs and no ext_state (these scenes have none), an instantiated agent
     count (orca_scenes.PIPE_TILE), closest_first sorting; external actions and a static map do not matter to it"""
     return cls != "s" or variant.startswith("first")
 

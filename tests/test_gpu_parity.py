@@ -301,7 +301,7 @@ def test_rollout_equals_repeated_steps(E, T):
 
 # ---------------------------------------------------------------- the metric geometry itself (4096 x 10 and its neighbours)
 def _pipe_tile(N, E):
-    """envs per tile of the pipelined kernel (launch_pipe, csrc/cagpu.hip): 4 for N = 10 at every batch size (1- / 2- /
+    """envs per tile of the pipelined kernel (launch_pipe, csrc/cagpu_launch.inc): 4 for N = 10 at every batch size (1- / 2- /
     3-env tiles for small batches measured slower in round 4), floor(64 / N) for the other agent counts"""
     return 4 if N == 10 else 64 // N
 
