@@ -14,6 +14,7 @@ AT_GOAL, WAS_AT_GOAL, IN_COLLISION, WAS_IN_COLLISION, OUT_OF_TIME, DONE, IS_LEAR
     1 << 0, 1 << 1, 1 << 2, 1 << 3, 1 << 4, 1 << 5, 1 << 6, 1 << 7)
 POLICY_SHIFT, DYNAMICS_SHIFT = 8, 12
 ABSENT, PLAN_VALID = 1 << 16, 1 << 17
+RVO_NONCOOP = 1 << 18   # CA_RVO_NONCOOP: written only by launches with a CaRvoDraw whose collab_coeff < 0
 ABI_VERSION = 12  # CAGPU_VERSION of include/cagpu.h: the struct layouts below mirror THAT header
 POL_RVO, POL_NONCOOP, POL_STATIC, POL_EXTERNAL, POL_LEARNING, POL_LEARNING_GA3C, POL_GA3C_CADRL = range(7)
 DYN_UNICYCLE, DYN_MAX_TURN_RATE, DYN_EXTERNAL = range(3)
@@ -108,6 +109,15 @@ class CaActionTape(C.Structure):
     _fields_ = [("actions", _P), ("step_stride", C.c_int64)]
 
 
+class CaRvoDraw(C.Structure):
+    """RVOPolicy's stochastic branches drawn in the step kernels (cagpu_step_noise); include/cagpu.h states the rule"""
+    _fields_ = [("seed", C.c_uint64), ("collab_coeff", C.c_double), ("anti_collab_t", C.c_double), ("noise_std", C.c_double),
+                ("noise_mask", _P), ("address", _P)]
+
+
+FAULT_RVO_DRAW_STEP = 16   # bit 4 of the fault word: an agent was queried under a CaRvoDraw at an episode step >= 2^22
+
+
 class CaPoseRing(C.Structure):
     """the pose ring of a fused launch (cagpu_tape_poses): slot t = the poses after step t; include/cagpu.h states the rule"""
     _fields_ = [(n, _P) for n in ("pos_x", "pos_y", "heading", "radius", "step_num", "env_map")]
@@ -163,7 +173,7 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes", "cagpu_ga3c_query", "cagpu_ga3c_value",
            "cagpu_generate_cases_at", "cagpu_stream_refill", "cagpu_episode_metrics_carry_bytes", "cagpu_episode_metrics",
            "cagpu_step_ex_maps", "cagpu_map_draw", "cagpu_heading_draw", "cagpu_policy_draw_at", "cagpu_step_tape",
-           "cagpu_tape_poses", "cagpu_laserscan_slots", "cagpu_laserscan_history")
+           "cagpu_tape_poses", "cagpu_laserscan_slots", "cagpu_laserscan_history", "cagpu_step_noise", "cagpu_rvo_draw_at")
 
 _lib = None
 
@@ -215,6 +225,9 @@ def lib():
     L.cagpu_policy_draw.argtypes = [PP, PS, PO, PA, C.POINTER(CaPolicyDraw), _P, _P]
     L.cagpu_step_ex_maps.argtypes = [PP, PS, PO, _P, PA, C.POINTER(CaStepEx), C.POINTER(CaPolicyDraw), _P]
     L.cagpu_step_tape.argtypes = [PP, PS, PO, C.POINTER(CaActionTape), PA, C.POINTER(CaStepEx), C.POINTER(CaPolicyDraw), _P]
+    L.cagpu_step_noise.argtypes = [PP, PS, PO, C.POINTER(CaActionTape), PA, C.POINTER(CaStepEx), C.POINTER(CaPolicyDraw),
+                                   C.POINTER(CaRvoDraw), _P]
+    L.cagpu_rvo_draw_at.argtypes = [C.POINTER(CaRvoDraw), C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P]
     L.cagpu_map_draw.argtypes = [C.c_uint64, C.c_int32, _P, _P, C.c_int64, _P, _P]
     L.cagpu_heading_draw.argtypes = [C.c_uint64, C.c_int32, _P, _P, C.c_int64, _P, _P]
     L.cagpu_policy_draw_at.argtypes = [C.POINTER(CaPolicyDraw), C.c_int32, _P, _P, _P, C.c_int64, _P, _P]

@@ -112,6 +112,7 @@ class BatchedSim(object):
         self.orca_vel = z((E, N, 2), torch.float32) if record_actions else None
         self._cs = nat.CaState(**{n: self._state[n].data_ptr() for n in nat.STATE_FIELDS if n in self._state})
         self._rvo = None          # RVOPolicy's stochastic branches (set_rvo_stochastic)
+        self._rd = None           # ... drawn inside the step kernels instead (set_rvo_draw: CaRvoDraw)
         self._variants = []       # per-agent sensor arguments beyond the primary pair (set_sensor_variants)
         if not self.pipeline:
             self._cs.next_action = None
@@ -270,6 +271,9 @@ class BatchedSim(object):
         Both None: switched off (the deterministic kernels, pipelined plan included).  The reference draws from numpy's
         global stream, one agent after the other: the batched draws are the same distributions, not the same numbers."""
         self.sync()
+        if self._rd is not None and not (heading_noise is None and (collab_coeff is None or collab_coeff >= 0)):
+            raise ValueError("set_rvo_stochastic: the batch draws these branches inside the step kernels (set_rvo_draw); "
+                             "switch that off first -- one source of the numbers per batch")
         # (whichever branch is not configured below must not keep pointing at a tensor of an earlier configuration)
         self._cs.rvo_collab = None
         self._cs.rvo_heading_noise = None
@@ -305,6 +309,68 @@ class BatchedSim(object):
             z = torch.randn((self.E, self.N), generator=r["gen"], device=self.device, dtype=torch.float64)
             r["noise"] = (z * r["std"] * r["mask"]).contiguous()
             self._cs.rvo_heading_noise = r["noise"].data_ptr()
+
+    def set_rvo_draw(self, seed, heading_noise=None, collab_coeff=None, anti_collab_t=1.0, noise_std=0.5, _address=None):
+        """set_rvo_stochastic's two branches drawn INSIDE the step kernels (CaRvoDraw of include/cagpu.h states the rule):
+        every draw is a pure function of (seed, global env id, episode, agent slot, episode step), so nothing happens between
+        two steps -- step(), rollout() with action tapes / keep_steps / map_sensors, the look-ahead ring, a rewind's replay,
+        every shard layout and replay() see the same numbers.  The arguments are set_rvo_stochastic's; `seed` must be != 0 and
+        differ from the table's heading_seed, the policy draw's seed and the map set's map_seed.  Both branches off
+        (heading_noise None and collab_coeff None or >= 0): switched off.  Having set_rvo_stochastic on as well is a
+        ValueError.  The anti-collaborative bit of every agent is bit 18 of its flag word: rvo_noncoop()."""
+        self.sync()
+        if self._la is not None:
+            self._la["in_kernel"].clear()
+            self._la["prep"] = None
+        self.invalidate_plan()
+        c = None if (collab_coeff is None or not collab_coeff < 0) else float(collab_coeff)
+        if heading_noise is None and c is None:
+            self._rd = None
+            return
+        if self._rvo is not None:
+            raise ValueError("set_rvo_draw: set_rvo_stochastic is on for this batch (draws on the host side of every launch); "
+                             "switch it off first -- one source of the numbers per batch")
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        taken = [0]
+        if self._ar is not None:
+            taken.append(int(self._ar.heading_seed))
+        if self._draw is not None:
+            taken.append(int(self._draw["c"].seed))
+        if self._maps is not None:
+            taken.append(int(self._maps.map_seed))
+        if seed in taken:
+            raise ValueError("set_rvo_draw: seed must be != 0 and differ from the table's heading_seed, the policy draw's seed "
+                             "and the map set's map_seed")
+        if c is not None and not float(anti_collab_t) > 0:
+            raise ValueError("set_rvo_draw: anti_collab_t must be > 0")
+        if not float(noise_std) >= 0:
+            raise ValueError("set_rvo_draw: noise_std must be >= 0")
+        mask = None
+        if heading_noise is not None:
+            mask = torch.from_numpy(np.array(np.broadcast_to(np.asarray(heading_noise, bool), (self.E, self.N)))
+                                    .astype(np.uint8)).to(self.device).contiguous()
+        addr = None if _address is None else self._dev(np.ascontiguousarray(_address, np.int64).reshape(self.E, 2), torch.int64)
+        d = nat.CaRvoDraw(seed=seed, collab_coeff=0.0 if c is None else c, anti_collab_t=float(anti_collab_t),
+                          noise_std=float(noise_std), noise_mask=None if mask is None else mask.data_ptr(),
+                          address=None if addr is None else addr.data_ptr())
+        tape = nat.CaActionTape()
+        self._rd = dict(c=d, ref=C.byref(d), mask=mask, addr=addr, tape=tape, tape_ref=C.byref(tape),
+                        args=dict(seed=seed, collab_coeff=c, anti_collab_t=float(anti_collab_t), noise_std=float(noise_std)))
+
+    def _noise(self, p, s, o, ext, ar, sx, stream, stride=0):
+        """the one native call of a batch with set_rvo_draw: cagpu_step_noise (every launch form goes through here)"""
+        rd = self._rd
+        tape_ref = None
+        if ext is not None:
+            rd["tape"].actions, rd["tape"].step_stride = ext, stride
+            tape_ref = rd["tape_ref"]
+        return self.lib.cagpu_step_noise(p, s, o, tape_ref, ar, sx, None if self._draw is None else self._draw["ref"],
+                                         rd["ref"], stream)
+
+    def rvo_noncoop(self):
+        """bool [E, N]: RVOPolicy's `use_non_coop_policy` of every agent slot as the step last handed out left it (bit 18 of
+        the flag word, CA_RVO_NONCOOP; through sync()).  All False without set_rvo_draw(collab_coeff < 0)."""
+        return (self.state["flags"] & nat.RVO_NONCOOP) != 0
 
     def set_sensor_variants(self, variants=None):
         """Agents of one batch whose OtherAgentsStatesSensor arguments differ (the reference gives every agent its own
@@ -735,6 +801,8 @@ class BatchedSim(object):
 
     def _launch_n(self, p, s, o, ext, ar, sx, stream):
         """a fused launch: _launch, or -- where the CaStepEx names a map or a set -- cagpu_step_ex_maps with the draw"""
+        if self._rd is not None:   # (set_rvo_draw: cagpu_step_noise carries maps, tape and draw alike)
+            return self._noise(p, s, o, ext, ar, sx, stream)
         if self._map is None:
             return self._launch(p, s, o, ext, ar, sx, stream)
         return self._step_ex_maps(p, s, o, ext, ar, sx, None if self._draw is None else self._draw["ref"], stream)
@@ -1011,7 +1079,8 @@ class BatchedSim(object):
             if self._cstream["since"] >= self._cstream["every"]:
                 self._stream_refill()
             self._cstream["since"] += 1
-        rc = self._launch(self._p_ref, self._cs_ref, self._co_ref, ext, self._ar_ref, self._sx_ref, self._stream_handle())
+        rc = (self._launch if self._rd is None else self._noise)(self._p_ref, self._cs_ref, self._co_ref, ext, self._ar_ref,
+                                                                  self._sx_ref, self._stream_handle())
         if rc != 0:
             nat.check(rc)
         if fast:
@@ -1108,7 +1177,8 @@ class BatchedSim(object):
         slot t (cagpu_step_tape) -- the step of the CALL, not of the episode: an env that auto-resets in step t plays slot
         t + 1 as the first action of its next episode.  Entries of agents that are not queried (internal policies, done
         agents, absent slots) are never read.  Where the batch needs work between two steps (a GA3C-CADRL network, stochastic
-        RVO draws) the steps are single launches and step t is handed slot t: the same results, one launch per step.
+        RVO draws of set_rvo_stochastic -- not those of set_rvo_draw, which the step kernels make themselves) the steps are
+        single launches and step t is handed slot t: the same results, one launch per step.
         keep_steps: every step keeps its outputs (a ring launch, CaStepEx.ring, into newly allocated tensors) and the call
         returns (obs [n, E, N, W], rewards [n, E, N], done [n, E, N], game_over [n, E]); `obs` / `rewards` / `done` /
         `game_over` afterwards show the last slot.  With keep_final() on every slot has its own final block: `kept_final` =
@@ -1174,7 +1244,10 @@ class BatchedSim(object):
             co_ref, fin = C.byref(co), None if cf is None else C.addressof(cf)
         sx = nat.CaStepEx(n_steps=n, ring=1 if keep_steps else 0, map=self._sx.map, set=self._sx.set,
                           traj=None if ct is None else C.addressof(ct), fin=fin, log=self._sx.log)
-        if stride:
+        if stride and self._rd is not None:
+            nat.check(self._noise(self._p_ref, self._cs_ref, co_ref, e.data_ptr(), self._ar_ref, C.byref(sx),
+                                  self._stream_handle(), stride))
+        elif stride:
             tape = nat.CaActionTape(actions=e.data_ptr(), step_stride=stride)
             nat.check(self.lib.cagpu_step_tape(self._p_ref, self._cs_ref, co_ref, C.byref(tape), self._ar_ref, C.byref(sx),
                                                None if self._draw is None else self._draw["ref"], self._stream_handle()))
@@ -1227,7 +1300,8 @@ class BatchedSim(object):
     def lookahead_ok(self):
         """can step_lookahead() run this batch?  Every policy has to be answered inside the step kernel and nothing may
         happen BETWEEN two steps on the host or in another kernel: no GA3C-CADRL network, no per-step stochastic RVO
-        draws, no per-agent sensor variants (extra cagpu_observe launches).  A static map or a map set is carried by the
+        draws (set_rvo_stochastic; set_rvo_draw draws inside the step kernels and is fine), no per-agent sensor variants
+        (extra cagpu_observe launches).  A static map or a map set is carried by the
         ring's launches (walls and map draws are those of single steps); laserscan() / occupancy_grid() go through sync()
         and describe the step last handed out."""
         return not (self._has_ga3c or self._rvo is not None or self._variants)
@@ -1383,7 +1457,8 @@ class BatchedSim(object):
             rc = self.lib.cagpu_ring_snapshots(self._p_ref, self._cs_ref, C.byref(co), ar_ref, k)
             if rc < 0:
                 nat.check(rc)
-            in_kernel = la["in_kernel"][key] = rc == 1
+            # (a batch with set_rvo_draw never runs the pipelined kernel: the rewind point is the device copy)
+            in_kernel = la["in_kernel"][key] = rc == 1 and self._rd is None
         sx = nat.CaStepEx(n_steps=k, ring=1, snapshot_delta=(la["snap"].data_ptr() - self._slab.data_ptr()) if in_kernel else 0,
                           map=self._sx.map, set=self._sx.set, fin=None if cf is None else C.addressof(cf), log=self._sx.log)
         return dict(k=k, key=key, ring=ring, co=co, co_ref=C.byref(co), ar_ref=ar_ref, in_kernel=in_kernel, slots=slots,
@@ -1778,6 +1853,10 @@ class BatchedSim(object):
                 child.set_occupancy_grid(self._occ.x_width, self._occ.y_width,
                                          packed=False if self.occ_bits is None else (True if self.occ is None else "both"))
         child.set_fixture_table(start["cases"], env_id_offset=0, case_stride=M, heading_seed=0)
+        if self._rd is not None:   # the parent's RVO draw under the episodes' own addresses (CaRvoDraw.address)
+            mask = None if self._rd["mask"] is None else self._rd["mask"].index_select(0, torch.as_tensor(env, device=dev)).cpu().numpy() != 0
+            child.set_rvo_draw(heading_noise=mask, _address=np.stack([pl["global_env"], pl["episode"]], axis=1),
+                               **self._rd["args"])
         child.keep_final(True)
         child.log_episodes(capacity=capacity)
         if record:

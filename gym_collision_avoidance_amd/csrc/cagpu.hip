@@ -112,6 +112,12 @@ struct KArgs {
   // an n-step launch reads ext + t * ext_stride (a kernel argument times the loop counter: scalar registers); where a rollout
   // is n launches the host advances `ext` itself (ring_advance).  Appended, like the draw
   int64_t ext_stride;
+  // RVO draw (cagpu_step_noise; rd_seed == 0 everywhere else): the members of CaRvoDraw.  Appended, like the tape; the
+  // pipelined kernels never see a launch with it (pipe_eligible)
+  unsigned long long rd_seed;
+  double rd_c, rd_T, rd_std;
+  const uint8_t* rd_mask;
+  const int64_t* rd_addr;
 };
 
 // One agent's share of an episode-log record (CaEpLog): env e ends its episode number `ep` (its reset count before the
@@ -774,7 +780,10 @@ __device__ __forceinline__ void reset_lane(Lane& r, const double* c, const bool 
 // MSET: the n-step form (MULTI) also runs the map-set code of the single-step form -- the per-env grid of A3, the map draw
 // of an auto-reset.  A template flag that only a set launch with n_steps > 1 selects (main_variant in cagpu_launch.inc): every other
 // instantiation is the code it was before the flag existed.
-template <int NT, bool STAGE, int NC, bool MULTI, bool RO, int TE = 0, bool MSET = false>
+// RD: the RVO draw (CaRvoDraw) -- instantiations of their own, of the general form (NC = 0) only, which nothing but a launch
+// with a draw selects: behind a uniform test of the seed inside the existing instantiations the draw measured 18.0 -> 18.5 us
+// per single step and 13.5 -> 13.7 per fused step at 4096 x 10 WITHOUT a draw (profiles/rvo_draw.md), outside the parent's spread.
+template <int NT, bool STAGE, int NC, bool MULTI, bool RO, int TE = 0, bool MSET = false, bool RD = false>
 // n-step: <= 128 VGPRs (four 4-wave workgroups per CU) -- except N = 20, whose single-step form already needs 172 (two
 // workgroups per CU either way): held to 128 its n-step form spilled ~200 VGPRs to scratch around the step loop
 __global__ __launch_bounds__(NT, MULTI ? (NC == 20 ? 2 : 4) : 1) void ca_kernel(const KArgs k) {
@@ -925,6 +934,13 @@ __global__ __launch_bounds__(NT, MULTI ? (NC == 20 ? 2 : 4) : 1) void ca_kernel(
           sh_q3[0] = 0;
           sh_q3[ROW + 1] = __popcll(qm);
         }
+        // RVO draw (CaRvoDraw; the RD instantiations): the ego's collaboration coefficient of this query, handed
+        // to the pair lanes through sh_vrx -- free until the 1-D programmes' results land there behind the next two barriers
+        if (RD) {
+          float cf = static_cast<float>(p.rvo_collab_coeff);
+          if (rvo) cf = rvo_collab_draw(k, rvo_addr(k, e, reset_cnt), a, r.step_num, r.t, r.flags);
+          sh_vrx[lane] = cf;
+        }
       }
       WG_SYNC();
       F2 v_orca = f2(0.f, 0.f);  // this lane's ORCA velocity (agent wave)
@@ -989,7 +1005,7 @@ __global__ __launch_bounds__(NT, MULTI ? (NC == 20 ? 2 : 4) : 1) void ca_kernel(
           if (jo == 0) sh_nb[ag] = n;
           if (dj < INFINITY && rank < n) {
             // (the ego's own collaboration coefficient where the caller drew one per agent: RVOPolicy.py:77-90)
-            const float cf = k.s.rvo_collab ? k.s.rvo_collab[env0 * N + ag] : collab;
+            const float cf = RD ? sh_vrx[ag] : (k.s.rvo_collab ? k.s.rvo_collab[env0 * N + ag] : collab);
             Lmat[rank * CS + ag] = half_plane_sel(mpos, f2(sh_fvx[ag], sh_fvy[ag]), sh_frad[ag],
                                                    f2(sh_fpx[eb + j], sh_fpy[eb + j]), f2(sh_fvx[eb + j], sh_fvy[eb + j]),
                                                    sh_frad[eb + j], cf, inv_h, inv_dt);
@@ -1165,6 +1181,7 @@ LP1_UNROLL
             const float ts = static_cast<float>(p.rvo_dt);
             rvo_action(sh_fpx[lane], sh_fpy[lane], v_orca, ts, r.px, r.py, r.heading, k.inv_rvo_dt, spd, dh);
             if (k.s.rvo_heading_noise) dh = dh + k.s.rvo_heading_noise[i];  // RVOPolicy.py:118-119 (drawn by the caller)
+            if (RD && k.rd_mask) dh = dh + rvo_heading_noise(k, rvo_addr(k, e, reset_cnt), a, r.step_num, i);  // (drawn here)
           } else if (pol == CA_POL_NONCOOP) {  // NonCooperativePolicy.py:21
             const Ego eg = ego_frame(r.px, r.py, r.gx, r.gy, r.heading);
             spd = r.ps;
@@ -1518,6 +1535,7 @@ LP1_UNROLL
                                          reset_cnt, a, N, [&](const int j) { return !p.ragged || rad[j * 6] > 0.0; }, r.flags);
               if (RO) sh_flag[lane] = r.flags;  // (the copy of the reset observation takes is_learning from here)
             }
+            if (RD && k.rd_c < 0.0) r.flags &= ~static_cast<uint32_t>(CA_RVO_NONCOOP);  // RVO draw: a new episode starts without the bit
             // a map set with a key: the env's next map (CaMapSet.map_seed), one plain store by its agent 0 lane
             if ((!MULTI || MSET) && k.map_seed && a == 0) k.env_map[e] = map_draw(k.map_seed, k.env_id_offset + e, reset_cnt, k.num_maps);
             ep_step = 0;

@@ -63,6 +63,7 @@ struct StepCall {
   const CaPolicyDraw* draw = nullptr;  // cagpu_step_draw
   bool maps_multi = false;             // cagpu_step_ex_maps: a map / map set with n_steps > 1 or ring is admitted
   const CaActionTape* tape = nullptr;  // cagpu_step_tape with step_stride != 0 (its `actions` is then the call's `ext`)
+  const CaRvoDraw* rd = nullptr;       // cagpu_step_noise
   // the record the entry point insists on (the older names: "traj may not be NULL" ...); cagpu_step_ex: none
   enum Need { NEED_NONE, NEED_SET, NEED_TRAJ, NEED_FIN, NEED_LOG } need = NEED_NONE;
   bool query_snapshot = false;   // cagpu_ring_snapshots: answer 1 / 0 instead of launching
@@ -167,6 +168,26 @@ static int step_impl(const CaParams* p, const CaState* s, const CaOut* o, const 
                              "num_agents%s");
     k.ext_stride = t.step_stride;
   }
+  if (c.rd) {  // (behind the tape's: the RVO draw's rejections are the last CA_EINVAL ones)
+    const CaRvoDraw& d = *c.rd;
+    if (s->rvo_collab || s->rvo_heading_noise)
+      return fail(CA_EINVAL, "cagpu_step_noise: CaState.rvo_collab / rvo_heading_noise beside a CaRvoDraw (one source of these numbers per launch)%s");
+    if (d.seed == 0) return fail(CA_EINVAL, "cagpu_step_noise: CaRvoDraw.seed must not be 0%s");
+    if ((ar && d.seed == ar->heading_seed) || (c.draw && d.seed == c.draw->seed) || (set && d.seed == set->map_seed))
+      return fail(CA_EINVAL, "cagpu_step_noise: CaRvoDraw.seed equals CaAutoReset.heading_seed, CaPolicyDraw.seed or CaMapSet.map_seed "
+                             "(two rules would read the same uniforms)%s");
+    if (d.collab_coeff < 0.0 && !(d.anti_collab_t > 0.0))
+      return fail(CA_EINVAL, "cagpu_step_noise: CaRvoDraw.anti_collab_t must be > 0 with collab_coeff < 0%s");
+    if (!(d.noise_std >= 0.0)) return fail(CA_EINVAL, "cagpu_step_noise: CaRvoDraw.noise_std must be >= 0%s");
+    if (!(d.collab_coeff < 0.0) && !d.noise_mask)
+      return fail(CA_EINVAL, "cagpu_step_noise: both branches of the CaRvoDraw are off (collab_coeff not < 0 and noise_mask NULL)%s");
+    if (reinterpret_cast<uintptr_t>(d.address) & 7u)
+      return fail(CA_EINVAL, "cagpu_step_noise: CaRvoDraw.address must be 8-byte aligned%s");
+    k.rd_seed = d.seed; k.rd_c = d.collab_coeff; k.rd_T = d.anti_collab_t; k.rd_std = d.noise_std;
+    k.rd_mask = d.noise_mask; k.rd_addr = d.address;
+    k.s.next_action = nullptr;  // (the draw belongs to the query of the step that consumes it: no plan is read or left)
+    k.reset_plan = nullptr;
+  }
   k.inv_rvo_dt = 1.0 / p->rvo_dt;
   {
     static std::atomic<int> seq{0};
@@ -213,6 +234,32 @@ int cagpu_step_tape(const CaParams* p, const CaState* s, const CaOut* o, const C
   c.maps_multi = true;
   c.tape = tape;
   return step_impl(p, s, o, tape->actions, ar, c, stream);
+}
+
+int cagpu_step_noise(const CaParams* p, const CaState* s, const CaOut* o, const CaActionTape* tape, const CaAutoReset* ar,
+                     const CaStepEx* x, const CaPolicyDraw* d, const CaRvoDraw* rd, void* stream) {
+  if (!rd) return cagpu_step_tape(p, s, o, tape, ar, x, d, stream);
+  StepCall c = step_call("cagpu_step_ex_maps", x, d);  // (the older rules speak in that entry point's name, as for a tape)
+  c.maps_multi = true;
+  if (tape && tape->step_stride != 0) c.tape = tape;
+  c.rd = rd;
+  return step_impl(p, s, o, tape ? tape->actions : nullptr, ar, c, stream);
+}
+
+int cagpu_rvo_draw_at(const CaRvoDraw* rd, int32_t num_agents, const int64_t* g, const int32_t* k, const int32_t* a,
+                      const int32_t* s, int64_t n, uint8_t* out_noncoop_draw, double* out_noise, void* stream) {
+  if (!rd || !g || !k || !a || !s || (!out_noncoop_draw && !out_noise) || num_agents < 1 || num_agents > big::NT_MAX || n < 0)
+    return fail(CA_EINVAL, "cagpu_rvo_draw_at: NULL pointer, no output, num_agents outside 1..1024 or n < 0%s");
+  if (rd->seed == 0) return fail(CA_EINVAL, "cagpu_rvo_draw_at: CaRvoDraw.seed must not be 0%s");
+  if (!(rd->noise_std >= 0.0)) return fail(CA_EINVAL, "cagpu_rvo_draw_at: CaRvoDraw.noise_std must be >= 0%s");
+  if (n == 0) return CA_OK;
+  RvoDrawAtArgs q;
+  std::memset(&q, 0, sizeof(q));
+  q.seed = rd->seed; q.c = rd->collab_coeff; q.std = rd->noise_std;
+  q.g = g; q.k = k; q.a = a; q.s = s; q.n = static_cast<long>(n);
+  q.out_draw = out_noncoop_draw; q.out_noise = out_noise;
+  const unsigned grid = static_cast<unsigned>((n + 255) / 256);
+  return launch(rvo_draw_at_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), q);
 }
 
 int cagpu_map_draw(uint64_t seed, int32_t num_maps, const int64_t* env_ids, const int32_t* counts, int64_t n, int32_t* out,

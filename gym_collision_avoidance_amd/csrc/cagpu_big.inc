@@ -23,7 +23,8 @@ __host__ __device__ inline size_t ws_bytes_per_wg(int N) { return static_cast<si
 // LDS of one workgroup: 8 double + 5 float + 1 u32 arrays of NT elements (88 KB at 1024 threads: dynamic)
 __host__ __device__ inline size_t lds_bytes(int nt) { return static_cast<size_t>(nt) * (8 * 8 + 5 * 4 + 4); }
 
-template <int NT>
+// RD: the RVO draw (CaRvoDraw) has instantiations of its own, as in ca_kernel
+template <int NT, bool RD = false>
 __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char* ws, const size_t ws_per_wg) {
   extern __shared__ __attribute__((aligned(16))) unsigned char big_smem[];
   double* sh_px = reinterpret_cast<double*>(big_smem);
@@ -104,12 +105,15 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
           const double gvx = r.gx - r.px, gvy = r.gy - r.py;
           const double sc = divd(r.ps, sqrtd(gvx * gvx + gvy * gvy));  // RVOPolicy.py:66-67
           const F2 pref = f2(static_cast<float>(sc * gvx), static_cast<float>(sc * gvy));
-          const float collab = k.s.rvo_collab ? k.s.rvo_collab[i] : static_cast<float>(p.rvo_collab_coeff);  // :86-90
+          float collab = k.s.rvo_collab ? k.s.rvo_collab[i] : static_cast<float>(p.rvo_collab_coeff);  // :86-90
+          // RVO draw (CaRvoDraw; the RD instantiations): the coefficient and, below, the noise are drawn here
+          if (RD) collab = rvo_collab_draw(k, rvo_addr(k, e, reset_cnt), a, r.step_num, r.t, r.flags);
           v_orca = orca_velocity<NT>(sh_fpx, sh_fpy, sh_fvx, sh_fvy, sh_frad, 0, a, N, pref, static_cast<float>(r.ps), collab,
                                      static_cast<float>(p.rvo_time_horizon), static_cast<float>(p.rvo_dt),
                                      static_cast<float>(p.sensing_horizon), p.rvo_max_neighbors, fcol, Lcol, Pcol);
           rvo_action(sh_fpx[a], sh_fpy[a], v_orca, static_cast<float>(p.rvo_dt), r.px, r.py, r.heading, k.inv_rvo_dt, spd, dh);
           if (k.s.rvo_heading_noise) dh = dh + k.s.rvo_heading_noise[i];  // :118-119 (drawn by the caller)
+          if (RD && k.rd_mask) dh = dh + rvo_heading_noise(k, rvo_addr(k, e, reset_cnt), a, r.step_num, i);
         } else if (pol == CA_POL_NONCOOP) {  // NonCooperativePolicy.py:21
           const Ego eg = ego_frame(r.px, r.py, r.gx, r.gy, r.heading);
           spd = r.ps;
@@ -333,6 +337,7 @@ __global__ __launch_bounds__(NT) void ca_big_kernel(const KArgs k, unsigned char
                       reset_cnt - 1, sh_r0[a], sh_r1[a], sh_r2[a], r.flags, ep_step, any_coll, all_goal);
         reset_lane(r, k.table + (c * N + a) * 6, k.heading_seed != 0, h0, p);
         if (drawn >= 0) r.flags = (r.flags & ~0xFC0u) | (k.draw_bits[drawn] & 0xFC0u);
+        if (RD && k.rd_c < 0.0) r.flags &= ~static_cast<uint32_t>(CA_RVO_NONCOOP);  // RVO draw: a new episode starts without the bit
         statics_dirty = true;
         do_sense = true;
       }

@@ -71,6 +71,22 @@ __device__ __forceinline__ double uniform_at(unsigned long long seed, unsigned c
   return (static_cast<double>(c0 >> 5) * 67108864.0 + static_cast<double>(c1 >> 6)) / 9007199254740992.0;
 }
 
+// both uniforms of the same block: words 0, 1 -> ua (uniform_at's), words 2, 3 -> ub (the step kernels' RVO draw, CaRvoDraw)
+__device__ __forceinline__ void uniform2_at(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3,
+                                            double& ua, double& ub) {
+  unsigned k0 = static_cast<unsigned>(seed), k1 = static_cast<unsigned>(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+    const unsigned n0 = static_cast<unsigned>(p1 >> 32) ^ c1 ^ k0, n1 = static_cast<unsigned>(p1);
+    const unsigned n2 = static_cast<unsigned>(p0 >> 32) ^ c3 ^ k1, n3 = static_cast<unsigned>(p0);
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  ua = (static_cast<double>(c0 >> 5) * 67108864.0 + static_cast<double>(c1 >> 6)) / 9007199254740992.0;
+  ub = (static_cast<double>(c2 >> 5) * 67108864.0 + static_cast<double>(c3 >> 6)) / 9007199254740992.0;
+}
+
 __device__ __forceinline__ double norm2(double x, double y) { return sqrt(x * x + y * y); }
 
 // gen_rand_testcases.py:91-108

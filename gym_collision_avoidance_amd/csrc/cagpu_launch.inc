@@ -126,6 +126,7 @@ void last_kernel_add(const char* word) {
 void map_suffix(const KArgs& k, const bool mset = false) {
   last_kernel_add(mset ? " set" : ((k.env_map || k.map.static_bits) ? " map" : ""));
   if (k.ext_stride) last_kernel_add(" tape");
+  if (k.rd_seed) last_kernel_add(" noise");  // (an RVO draw, CaRvoDraw: only the kernels that come through here run one)
 }
 
 // ---- ca_kernel: the instantiation a launch runs, in two steps.  main_geometry: N and the tile size compiled in (NC, TE)
@@ -150,8 +151,21 @@ MainKernel main_variant(const bool multi, const bool ro, const bool mset) {
   return {kernel_of<&ca_kernel<NT, STAGE, NC, false, false, TE>>(), NC, TE};
 }
 
+// ... with an RVO draw (CaRvoDraw): the RD instantiations, which exist in the general form (NC = 0: any N, the tile size read
+// from the arguments) only; the n-step one is the MSET form, which carries a set where there is one and costs nothing without
+template <int NT, bool STAGE>
+MainKernel main_variant_rd(const bool multi, const bool ro) {
+  if (multi) {
+    if (ro) return {kernel_of<&ca_kernel<NT, STAGE, 0, true, true, 0, true, true>>(), 0, 0};
+    return {kernel_of<&ca_kernel<NT, STAGE, 0, true, false, 0, true, true>>(), 0, 0};
+  }
+  if (ro) return {kernel_of<&ca_kernel<NT, STAGE, 0, false, true, 0, false, true>>(), 0, 0};
+  return {kernel_of<&ca_kernel<NT, STAGE, 0, false, false, 0, false, true>>(), 0, 0};
+}
+
 template <int NT, bool STAGE>
 MainKernel main_geometry(const KArgs& k, const bool multi, const bool ro, const bool mset) {
+  if (k.rd_seed) return main_variant_rd<NT, STAGE>(multi, ro);
   if constexpr (NT <= 256) {  // the 512-thread geometry exists for large N only
     if (k.p.num_agents == 10) {  // N and the tile size compiled in
       if (k.tile_envs == ROW / 10) return main_variant<NT, STAGE, 10>(multi, ro, mset);
@@ -229,6 +243,7 @@ bool pipe_eligible(const KArgs& k) {
   const int n = k.p.num_agents;
   if (!k.s.next_action || k.stage_obs) return false;
   if (k.s.rvo_collab || k.s.rvo_heading_noise || k.s.ext_state) return false;  // (per-step inputs belong to the step that consumes them)
+  if (k.rd_seed) return false;  // (an RVO draw, CaRvoDraw, is made by the query of the step that consumes it: no plan ahead)
   if (!(n == 10 || n == 8 || n == 6 || n == 5 || n == 4 || n == 3 || n == 2)) return false;  // (the instantiations)
   if (k.mode != MODE_STEP && k.mode != pipe::MODE_PLAN) return false;
   if (k.p.sort_mode != CA_SORT_CLOSEST_FIRST) return false;
@@ -347,8 +362,11 @@ int launch_big(const KArgs& k0, hipStream_t st) {
   std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ca_big_kernel grid=%ld threads=%d ws_per_wg=%zu mode=%d", wgs, nt, per,
                 k.mode);
   map_suffix(k);
-  const auto kernel = nt == 256 ? kernel_of<&big::ca_big_kernel<256>>()
-                                : (nt == 512 ? kernel_of<&big::ca_big_kernel<512>>() : kernel_of<&big::ca_big_kernel<1024>>());
+  const auto plain = nt == 256 ? kernel_of<&big::ca_big_kernel<256>>()
+                               : (nt == 512 ? kernel_of<&big::ca_big_kernel<512>>() : kernel_of<&big::ca_big_kernel<1024>>());
+  const auto kernel = !k.rd_seed ? plain   // (an RVO draw, CaRvoDraw: the RD instantiations)
+                      : (nt == 256 ? kernel_of<&big::ca_big_kernel<256, true>>()
+                                   : (nt == 512 ? kernel_of<&big::ca_big_kernel<512, true>>() : kernel_of<&big::ca_big_kernel<1024, true>>()));
   for (int s = 0; s < n_steps; ++s) {
     const int rc = launch_lds(kernel, dim3(static_cast<unsigned>(wgs)), dim3(nt), lds, st, k,
                               static_cast<unsigned char*>(k.o.workspace), per);

@@ -19,6 +19,27 @@ __global__ __launch_bounds__(256) void heading_draw_kernel(const unsigned long l
   out[i] = reset_heading(k, 0, counts[pair], a);
 }
 
+// cagpu_rvo_draw_at: one thread per address (g, k, a, s) of the RVO draw (CaRvoDraw) -- rvo_noncoop_draw / rvo_noise_draw of
+// cagpu_rules.inc, the functions the step kernels' queries call
+struct RvoDrawAtArgs {
+  unsigned long long seed;
+  double c, std;
+  const int64_t* g;
+  const int32_t *k, *a, *s;
+  long n;
+  uint8_t* out_draw;   // or nullptr
+  double* out_noise;   // or nullptr
+};
+__global__ __launch_bounds__(256) void rvo_draw_at_kernel(const RvoDrawAtArgs d) {
+  const long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= d.n) return;
+  const unsigned long long g = static_cast<unsigned long long>(d.g[i]);
+  const RvoAddr ad = {static_cast<unsigned>(g), static_cast<unsigned>(g >> 32), static_cast<unsigned>(d.k[i])};
+  const unsigned w3 = rvo_word3(d.a[i], d.s[i]);
+  if (d.out_draw) d.out_draw[i] = rvo_noncoop_draw(d.seed, ad, w3, d.c) ? 1 : 0;
+  if (d.out_noise) d.out_noise[i] = rvo_noise_draw(d.seed, ad, w3, d.std);
+}
+
 // one wave per pair (the ensure rule counts the pair's present slots): lane l settles slots l, l + 64, ...
 struct DrawAtArgs {
   const double* cdf;

@@ -150,3 +150,51 @@ __device__ __forceinline__ double reset_heading(const KArgs& k, const long env, 
   return -kPi + kTwoPi * gen::uniform_at(k.heading_seed, static_cast<unsigned>(ge), static_cast<unsigned>(ge >> 32),
                                          static_cast<unsigned>(reset_cnt), static_cast<unsigned>(a));
 }
+
+// ---- RVOPolicy's stochastic branches drawn in the step kernels (CaRvoDraw in cagpu.h has the rule; ca_kernel,
+// big::ca_big_kernel and rvo_draw_at_kernel call these).  A draw's address: (global env id, episode, agent slot, episode step).
+struct RvoAddr {
+  unsigned g0, g1, k;
+};
+__device__ __forceinline__ RvoAddr rvo_addr(const KArgs& k, const long env, const int reset_cnt) {
+  const unsigned long long g = static_cast<unsigned long long>(k.rd_addr ? k.rd_addr[2 * env] : k.env_id_offset + env);
+  const unsigned ep = k.rd_addr ? static_cast<unsigned>(k.rd_addr[2 * env + 1]) : static_cast<unsigned>(reset_cnt);
+  return {static_cast<unsigned>(g), static_cast<unsigned>(g >> 32), ep};
+}
+// counter word 3; an episode step outside the rule raises bit 4 of the fault word
+__device__ __forceinline__ unsigned rvo_word3(const int a, const int s) {
+  if (static_cast<unsigned>(s) >> 22) atomicOr(&g_fault, 16u);
+  return (static_cast<unsigned>(s) << 10) | static_cast<unsigned>(a);
+}
+// the clock lies within DT of a multiple of T: RVOPolicy.py:78-79 with numpy's round(x, 3) = rint(x * 1000) / 1000
+__device__ __forceinline__ bool rvo_redraw_window(const double t, const double T, const double dt) {
+  const double m = fmod(t, T);
+  return rint(m * 1000.0) / 1000.0 < dt || rint((T - m) * 1000.0) / 1000.0 < dt;
+}
+// what a redraw of use_non_coop_policy gives: np.random.choice([True, False], p=[1 - |c|, |c|]), RVOPolicy.py:80
+__device__ __forceinline__ bool rvo_noncoop_draw(const unsigned long long seed, const RvoAddr ad, const unsigned w3, const double c) {
+  double u0, u1;
+  gen::uniform2_at(seed, ad.g0, ad.g1, ad.k, w3, u0, u1);
+  return u0 < 1.0 - fabs(c);
+}
+// the number a masked agent adds to its delta heading: std * z, z standard normal (Box-Muller over u1 and the second block's v0)
+__device__ __forceinline__ double rvo_noise_draw(const unsigned long long seed, const RvoAddr ad, const unsigned w3, const double std) {
+  double u0, u1;
+  gen::uniform2_at(seed, ad.g0, ad.g1, ad.k, w3, u0, u1);
+  const double v0 = gen::uniform_at(seed, ad.g0, ad.g1, ad.k | 0x80000000u, w3);
+  return std * (sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * v0));
+}
+// The ego's collaboration coefficient of this query (RVOPolicy.py:77-90): redraws CA_RVO_NONCOOP in `flags` inside the window
+__device__ __forceinline__ float rvo_collab_draw(const KArgs& k, const RvoAddr ad, const int a, const int s, const double t,
+                                                 uint32_t& flags) {
+  if (!(k.rd_c < 0.0)) return static_cast<float>(k.p.rvo_collab_coeff);
+  if (rvo_redraw_window(t, k.rd_T, k.p.rvo_dt)) {
+    if (rvo_noncoop_draw(k.rd_seed, ad, rvo_word3(a, s), k.rd_c)) flags |= CA_RVO_NONCOOP;
+    else flags &= ~static_cast<uint32_t>(CA_RVO_NONCOOP);
+  }
+  return (flags & CA_RVO_NONCOOP) ? 0.0f : static_cast<float>(k.rd_c);
+}
+// ... and what it adds to its delta heading (RVOPolicy.py:118-119): +0.0 for an unmasked agent
+__device__ __forceinline__ double rvo_heading_noise(const KArgs& k, const RvoAddr ad, const int a, const int s, const long i) {
+  return k.rd_mask[i] ? rvo_noise_draw(k.rd_seed, ad, rvo_word3(a, s), k.rd_std) : 0.0;
+}

@@ -633,7 +633,14 @@ class CollisionAvoidanceEnv(Env):
                 for a_, agent in enumerate(g_):
                     if isinstance(agent.policy, RVOPolicy) and agent.policy.heading_noise:
                         noise[slice(None) if self._fixture is not None else e_, a_] = True
-            if noise.any() or Config.RVO_COLLAB_COEFF < 0:
+            on_device = getattr(self, "_rvo_device_seed", None)
+            if on_device is None and sim._rd is not None:
+                sim.set_rvo_draw(0)   # (switched off since the last upload)
+            if on_device is not None:   # draw_rvo_on_device(): the step kernels draw (core.BatchedSim.set_rvo_draw)
+                sim.set_rvo_stochastic()
+                sim.set_rvo_draw(on_device, heading_noise=noise if noise.any() else None, collab_coeff=Config.RVO_COLLAB_COEFF,
+                                 anti_collab_t=Config.RVO_ANTI_COLLAB_T)
+            elif noise.any() or Config.RVO_COLLAB_COEFF < 0:
                 # (the seed comes out of numpy's global stream, like the reference's own draws -- only when a stochastic
                 # branch is on: a deterministic batch must not shift the stream the scenario builders draw from)
                 self._rvo_seed = getattr(self, "_rvo_seed", 0) + 1
@@ -1274,6 +1281,16 @@ class CollisionAvoidanceEnv(Env):
                 out[n][li] = cols[n]
             out["metrics_dropped"] = int(met["dropped"])
         return out
+
+    def draw_rvo_on_device(self, seed):
+        """Batched mode: RVOPolicy's stochastic branches -- `heading_noise` policies, Config.RVO_COLLAB_COEFF < 0 -- are drawn
+        inside the step kernels as a pure function of (seed, global env id, episode, agent, episode step)
+        (core.BatchedSim.set_rvo_draw; include/cagpu.h CaRvoDraw) instead of by torch's generator before every launch:
+        step(None) is then served from the look-ahead ring, and rollout(n) and replay() work for such a batch.  seed: an int
+        != 0 (None: back to the per-launch draws).  Call before reset(); takes effect at the next reset()."""
+        if seed is not None and (int(seed) & 0xFFFFFFFFFFFFFFFF) == 0:
+            raise ValueError("draw_rvo_on_device: seed must be != 0")
+        self._rvo_device_seed = None if seed is None else int(seed)
 
     def replay(self, env_ids, episodes, **kw):
         """Run episodes of the batch again from their address -- `env_ids` (this shard's env indices, as episode_log()

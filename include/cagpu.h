@@ -62,7 +62,11 @@ enum {
   CA_ABSENT = 1u << 16,
   /* CaState.next_action holds this agent's action for the NEXT step (software-pipelined policy, see next_action).
    * Whoever writes the state arrays of an env directly must clear this bit for its agents (cagpu_reset does). */
-  CA_PLAN_VALID = 1u << 17
+  CA_PLAN_VALID = 1u << 17,
+  /* RVOPolicy's `use_non_coop_policy` (RVOPolicy.py:33,77-90) of an agent whose anti-collaborative branch is drawn inside
+   * the step kernels: written ONLY by launches with a CaRvoDraw whose collab_coeff < 0 (cagpu_step_noise), zero everywhere
+   * else.  While it is set the agent's ORCA query runs with collaboration coefficient 0. */
+  CA_RVO_NONCOOP = 1u << 18
 };
 /* policy plugin ids (test_cases.py:68-85 `policy_dict`) */
 enum {
@@ -272,7 +276,8 @@ typedef struct CaTraj {
  *   obs    the env's observation rows of the TERMINAL step, exactly as the step produced them (is_learning column included;
  *          the rows of absent slots are zeros) -- the `final_observation` / `terminal_observation` of the vector-env APIs;
  *   flags  the agents' flag words as they stand at the end of the terminal step (CA_AT_GOAL / CA_IN_COLLISION /
- *          CA_OUT_OF_TIME / CA_DONE / CA_ABSENT ... as decided by that step; CA_PLAN_VALID is unspecified).
+ *          CA_OUT_OF_TIME / CA_DONE / CA_ABSENT ... as decided by that step; CA_PLAN_VALID is unspecified; with a CaRvoDraw,
+ *          CA_RVO_NONCOOP -- bit 18 -- as the terminal step's query left it).
  * Rows of every OTHER env are LEFT ALONE (whatever the caller's buffer held): a row is valid where game_over says so.
  * Slots: the block advances exactly as the CaOut outputs do -- a ring call (every step keeps its outputs) writes step t's
  * records to block t of [n_steps, E, N, 6+7K] / [n_steps, E, N]; a plain cagpu_rollout_final (ring == 0: every step writes
@@ -296,7 +301,8 @@ typedef struct CaEpLog {
   double  *rows;   /* device [E, C, N, 4], 16-byte aligned.  Per agent slot:
                       0 total_reward (CaState.ep_reward), 1 time_to_goal (t), 2 extra_time_to_goal (t - slt)
                         -- 0..2 are exactly the three per-agent addends that the kernel sums into env_stats[e][5..7];
-                      3: the agent's flag word as the terminal step leaves it (what CaFinal.flags holds),
+                      3: the agent's flag word as the terminal step leaves it (what CaFinal.flags holds: with a
+                         CaRvoDraw that includes CA_RVO_NONCOOP, bit 18, as the step left it),
                          bit pattern in the low 32 bits of the 8 bytes, high 32 bits zero */
   int32_t *head;   /* device [E, C, 4], 16-byte aligned: {k, steps, case, outcome}
                       k       = reset_count[e] BEFORE the increment (index of the env's episode that just ended)
@@ -873,6 +879,69 @@ int cagpu_heading_draw(uint64_t heading_seed, int32_t num_agents, const int64_t 
 int cagpu_policy_draw_at(const CaPolicyDraw *d, int32_t num_agents, const int64_t *env_ids, const int32_t *counts,
                          const uint8_t *present, int64_t n, uint32_t *out_bits, void *stream);
 
+/* RVO DRAW (additive to v12): RVOPolicy's two stochastic branches -- anti-collaborative agents (RVOPolicy.py:77-90,
+ * Config.RVO_COLLAB_COEFF < 0) and `heading_noise` (RVOPolicy.py:118-119) -- drawn INSIDE the step kernels as a pure function
+ * of (seed, global env id, episode, agent slot, episode step), so that a batch with them runs in fused launches, a look-ahead
+ * ring, any shard layout and a replay with the same numbers.  (CaState.rvo_collab / rvo_heading_noise, the caller's own
+ * numbers for ONE step, stay as they are.)
+ *
+ * Address of a draw: the queried agent's
+ *   g  global env id: env_id_offset + e with a CaAutoReset, e without one;
+ *   k  episode: CaState.reset_count[e] as the step finds it (what the heading draw and the policy draw use);
+ *      `address` != NULL overrides both: env e draws as (g, k) = (address[2e], address[2e + 1]) whatever its reset count is
+ *      (a replay's child batch runs episode k of env g as its local env e);
+ *   a  agent slot, 0 .. num_agents - 1 <= 1023;
+ *   s  the agent's CaState.step_num as the query sees it (the pre-move state), 0 <= s < 2^22.  A queried agent with
+ *      s >= 2^22 is outside the rule: its draw uses the low 22 bits and bit 4 of the fault word is raised.
+ * Blocks: B0 = philox4x32_10(counter = (g & 0xFFFFFFFF, g >> 32, k, (s << 10) | a), key = (seed & 0xFFFFFFFF, seed >> 32)),
+ *         B1 = the same with counter word 2 = k | 0x80000000 (k >= 0: no episode's B0 is another's B1).
+ * Two words w, w' of a block give a uniform in [0, 1) with 53 bits: ((w >> 5) * 2^26 + (w' >> 6)) / 2^53.
+ *   u0 = B0 words 0, 1;  u1 = B0 words 2, 3;  v0 = B1 words 0, 1.
+ * Who draws: an agent that is QUERIED in the step -- present, not CA_DONE, policy CA_POL_RVO.  Every other slot draws
+ * nothing and its CA_RVO_NONCOOP bit is not touched by the query.
+ * Anti-collaboration (collab_coeff = c < 0, anti_collab_t = T, DT = CaParams.rvo_dt; all float64): with t the agent's clock
+ *   CaState.t before the move and m = fmod(t, T), the bit CA_RVO_NONCOOP of the agent's flag word is REDRAWN when
+ *       rint(m * 1000.0) / 1000.0 < DT   or   rint((T - m) * 1000.0) / 1000.0 < DT
+ *   (rint: to nearest, ties to even) as  bit = (u0 < 1.0 - fabs(c)),  and kept otherwise.  The query then runs ORCA with the
+ *   ego's collaboration coefficient 0.0f while the bit is set and (float)c otherwise (CaParams.rvo_collab_coeff is not
+ *   read).  t = 0 lies in the window, so the first query of every episode redraws; an auto-reset under such a CaRvoDraw
+ *   clears the bit of all slots of the env, which makes every episode a function of its start state and its address.
+ *   The bit is stored with the flag word the step stores anyway.  c >= 0 (or NaN): this branch is off, nothing reads or
+ *   writes the bit and the coefficient is CaParams.rvo_collab_coeff.
+ * Heading noise (noise_mask != NULL): the float64 delta heading of EVERY queried agent gets
+ *       dh = dh + (noise_mask[e * N + a] ? noise_std * z : 0.0),   z = sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * v0)
+ *   before it is rounded to the float32 action (an unmasked agent adds +0.0).  z is standard normal (Box-Muller); the
+ *   device's libm evaluates it, so it is reproducible on the device (cagpu_rvo_draw_at) and to a few ulp elsewhere.
+ * Kernels: the general kernel (single-step and n-step) and the large-env kernel; a launch with a CaRvoDraw never takes the
+ * pipelined kernel and is given no next_action / reset_plan plan.  cagpu_last_kernel() ends in " noise". */
+typedef struct CaRvoDraw {
+  uint64_t       seed;          /* != 0, != heading_seed, != the policy draw's seed, != map_seed */
+  double         collab_coeff;  /* < 0: anti-collaborative agents; >= 0: that branch is off */
+  double         anti_collab_t; /* Config.RVO_ANTI_COLLAB_T, > 0 (read where collab_coeff < 0) */
+  double         noise_std;     /* >= 0 (the reference: 0.5) */
+  const uint8_t *noise_mask;    /* device [E*N]; NULL = that branch off */
+  const int64_t *address;       /* device [2*E] (g, k) per env, 8-byte aligned, or NULL (above) */
+} CaRvoDraw;                    /* 48 bytes */
+
+/* cagpu_step_tape with a CaRvoDraw.  rd == NULL: exactly cagpu_step_tape -- the same launch, the same bits, the same
+ * cagpu_last_kernel() string.  With rd every rule of cagpu_step_tape holds in its own words, and BEHIND the tape's
+ * rejections in the order of first-reported errors stand, each CA_EINVAL with nothing launched:
+ *   CaState.rvo_collab / rvo_heading_noise beside a CaRvoDraw (one source of these numbers per launch);
+ *   seed == 0, or seed equal to CaAutoReset.heading_seed, CaPolicyDraw.seed or CaMapSet.map_seed of the call;
+ *   collab_coeff < 0 with anti_collab_t not > 0;  noise_std negative or NaN;
+ *   both branches off (collab_coeff not < 0 and noise_mask == NULL);  address not 8-byte aligned. */
+int cagpu_step_noise(const CaParams *p, const CaState *s, const CaOut *o, const CaActionTape *tape, const CaAutoReset *ar,
+                     const CaStepEx *x, const struct CaPolicyDraw *draw, const CaRvoDraw *rd, void *stream);
+
+/* The rule above for n arbitrary addresses, by the device functions the step kernels call: one thread per address
+ * (g[i], k[i], a[i], s[i]) -- device int64 / int32 / int32 / int32 [n] --
+ *   out_noncoop_draw[i] (device uint8, may be NULL) = (u0 < 1 - |collab_coeff|): what a redraw at that address gives;
+ *   out_noise[i]        (device double, may be NULL) = noise_std * z: what a MASKED agent adds (the mask is taken as "all").
+ * rd->noise_mask and rd->address are not read.  n == 0: nothing is launched.  CA_EINVAL, nothing launched: rd or an
+ * address array NULL, both outputs NULL, seed == 0, noise_std negative or NaN, num_agents outside 1..1024, n < 0. */
+int cagpu_rvo_draw_at(const CaRvoDraw *rd, int32_t num_agents, const int64_t *g, const int32_t *k, const int32_t *a,
+                      const int32_t *s, int64_t n, uint8_t *out_noncoop_draw, double *out_noise, void *stream);
+
 /* The policy query of the NEXT step ahead of time (collision_avoidance_env.py:305-323 for the built-in RVO policy):
  * fills s->next_action from the CURRENT state and sets CA_PLAN_VALID, without stepping.  cagpu_step / cagpu_rollout keep
  * the plan up to date by themselves; this entry point exists for states that did not come out of a step (the reset state
@@ -911,6 +980,8 @@ uint64_t cagpu_workspace_bytes(const CaParams *p);
  * bit 3 = an env of a case stream (CaCaseStream) auto-reset more than `window` times between two refills: it loaded a window
  * slot that still held an older episode, i.e. it REPEATED a scenario (valid memory, a valid case -- but not the stream's);
  * raised by cagpu_stream_refill's kernel.  A larger window, or shorter launches, avoid it.
+ * bit 4 = an agent was queried under a CaRvoDraw at an episode step s >= 2^22, outside the draw's address rule (its draw
+ * repeated the one of step s - 2^22).
  * *faults receives the word; clear != 0 resets it.  0 in normal operation; check it wherever the host synchronises anyway. */
 int cagpu_device_faults(uint32_t *faults, int32_t clear);
 
