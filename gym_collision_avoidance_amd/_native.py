@@ -118,6 +118,18 @@ class CaRvoDraw(C.Structure):
 FAULT_RVO_DRAW_STEP = 16   # bit 4 of the fault word: an agent was queried under a CaRvoDraw at an episode step >= 2^22
 
 
+class CaGa3cSample(C.Structure):
+    """the sampled GA3C-CADRL policy and the pre-step half of an experience tape slot (cagpu_ga3c_sample); include/cagpu.h
+    states the rule"""
+    _fields_ = [("seed", C.c_uint64), ("temperature", C.c_float), ("greedy", C.c_int32), ("mask", _P), ("agent_net", _P),
+                ("net_index", C.c_int32), ("reserved0", C.c_int32), ("address", _P), ("logits", _P), ("logp", _P),
+                ("entropy", _P), ("action", _P), ("obs", _P), ("value", _P), ("slot_obs", _P), ("slot_value", _P),
+                ("slot_live", _P), ("slot_address", _P)]
+
+
+FAULT_GA3C_SAMPLE_NAN = 32   # bit 5 of the fault word: a logits row with a NaN reached the sampler
+
+
 class CaPoseRing(C.Structure):
     """the pose ring of a fused launch (cagpu_tape_poses): slot t = the poses after step t; include/cagpu.h states the rule"""
     _fields_ = [(n, _P) for n in ("pos_x", "pos_y", "heading", "radius", "step_num", "env_map")]
@@ -173,7 +185,8 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_render", "cagpu_render_maps", "cagpu_render_work_bytes", "cagpu_ga3c_query", "cagpu_ga3c_value",
            "cagpu_generate_cases_at", "cagpu_stream_refill", "cagpu_episode_metrics_carry_bytes", "cagpu_episode_metrics",
            "cagpu_step_ex_maps", "cagpu_map_draw", "cagpu_heading_draw", "cagpu_policy_draw_at", "cagpu_step_tape",
-           "cagpu_tape_poses", "cagpu_laserscan_slots", "cagpu_laserscan_history", "cagpu_step_noise", "cagpu_rvo_draw_at")
+           "cagpu_tape_poses", "cagpu_laserscan_slots", "cagpu_laserscan_history", "cagpu_step_noise", "cagpu_rvo_draw_at",
+           "cagpu_ga3c_sample", "cagpu_ga3c_sample_at", "cagpu_gae")
 
 _lib = None
 
@@ -228,6 +241,10 @@ def lib():
     L.cagpu_step_noise.argtypes = [PP, PS, PO, C.POINTER(CaActionTape), PA, C.POINTER(CaStepEx), C.POINTER(CaPolicyDraw),
                                    C.POINTER(CaRvoDraw), _P]
     L.cagpu_rvo_draw_at.argtypes = [C.POINTER(CaRvoDraw), C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P]
+    L.cagpu_ga3c_sample.argtypes = [PP, PS, PA, C.POINTER(CaPolicyDraw), C.POINTER(CaMapSet), C.POINTER(CaRvoDraw),
+                                    C.POINTER(CaGa3cSample), _P, _P]
+    L.cagpu_ga3c_sample_at.argtypes = [C.c_uint64, C.c_float, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]
+    L.cagpu_gae.argtypes = [C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]
     L.cagpu_map_draw.argtypes = [C.c_uint64, C.c_int32, _P, _P, C.c_int64, _P, _P]
     L.cagpu_heading_draw.argtypes = [C.c_uint64, C.c_int32, _P, _P, C.c_int64, _P, _P]
     L.cagpu_policy_draw_at.argtypes = [C.POINTER(CaPolicyDraw), C.c_int32, _P, _P, _P, C.c_int64, _P, _P]

@@ -169,8 +169,18 @@ class BatchedSim(object):
         self._has_ga3c = False    # some agent's policy is CA_POL_GA3C_CADRL (set_plugins), or may become it (set_policy_draw)
         self._plugins_ga3c = False
         self._ga3c_ext = None
+        self._ga3c_ext2 = None    # the scratch action buffer of collect()'s last_value launch
         self.ga3c_logits = None
         self.ga3c_value = None    # float32 [E, N] (load_ga3c(keep_value=True)): logits_v of the agents ga3c() evaluated
+        # the sampled GA3C-CADRL policy (set_ga3c_sampling: CaGa3cSample) and the experience tape (collect)
+        self._samp = None         # dict(seed, temperature, mask, addr) / None = greedy
+        self._cg = nat.CaGa3cSample(temperature=1.0, greedy=1)
+        self._xp = None           # the tape slot the next ga3c() call fills: dict of addresses (collect) / None
+        self._samp_logits = None  # the sampler's own logits when load_ga3c did not keep them
+        self.ga3c_logp = None     # float32 [E, N]: log-probability of the index played in the last step (evaluated agents)
+        self.ga3c_entropy = None  # float32 [E, N]: entropy of the last step's softmax
+        self.ga3c_action = None   # int8 [E, N]: the index played
+        self.experience_max_bytes = 1 << 30   # the byte budget of ONE experience tape (collect)
         self._fault = None        # the non-blocking fault-word probe of the product path (_fault_probe)
         # (the first probe -- it creates the side stream and the pinned word: milliseconds -- on the second launch of a
         # simulator's life, not 256 launches in, in the middle of somebody's timed loop)
@@ -479,7 +489,9 @@ class BatchedSim(object):
         fused (default: self.ga3c_fused): the kernel computes the ego-centric observation of the agents it evaluates from
         the state arrays itself (cagpu_ga3c with obs = NULL: "obs + network inference fused in-kernel") instead of reading
         the rows the last step stored -- same bits; needs num_agents <= 32, no time_to_impact sorting and no per-agent
-        sensor variants."""
+        sensor variants.
+        With set_ga3c_sampling (or inside collect()) the sampler launch follows the network launch(es): the agents that
+        sample get their drawn index in `ext`, and ga3c_logp / ga3c_entropy / ga3c_action are written."""
         self.sync()
         if self._net is None:
             raise nat.CagpuError("GA3C-CADRL agents present but no network loaded: call load_ga3c() "
@@ -488,33 +500,41 @@ class BatchedSim(object):
             if self._ga3c_ext is None:
                 self._ga3c_ext = torch.zeros((self.E, self.N, 2), dtype=torch.float64, device=self.device)
             ext = self._ga3c_ext
-        lg = None if self.ga3c_logits is None else self.ga3c_logits.data_ptr()
+        sampler = self._samp is not None or self._xp is not None
+        if sampler and self.ga3c_logits is None and self._samp_logits is None:   # (the sampler reads the logits: its own copy)
+            self._samp_logits = torch.zeros((self.E, self.N, 11), dtype=torch.float32, device=self.device)
+        lgt = self.ga3c_logits if self.ga3c_logits is not None else (self._samp_logits if sampler else None)
+        lg = None if lgt is None else lgt.data_ptr()
         fused = self.ga3c_fused if fused is None else fused
         if fused and (self.N > 32 or self.p.sort_mode == nat.SORT_TIME_TO_IMPACT or self._variants):
             fused = False
         obs_ptr = None if fused else self._obs.data_ptr()
         if self.ga3c_value is not None:
-            return self._ga3c_with_value(ext, obs_ptr, lg)
-        if self._agent_net is None:      # one checkpoint (index 0) for every GA3C-CADRL agent
+            self._ga3c_with_value(ext, obs_ptr, lg)
+        elif self._agent_net is None:      # one checkpoint (index 0) for every GA3C-CADRL agent
             nat.check(self.lib.cagpu_ga3c(C.byref(self.p), C.byref(self._cs), obs_ptr, C.byref(self._net),
                                           ext.data_ptr(), lg, self._stream()))
-            return ext
-        for idx in sorted(self._nets):   # one launch per checkpoint, each over its own agents (CaNet.agent_net / net_index)
-            net = self._nets[idx][0]
-            net.agent_net, net.net_index = self._agent_net.data_ptr(), idx
-            nat.check(self.lib.cagpu_ga3c(C.byref(self.p), C.byref(self._cs), obs_ptr, C.byref(net),
-                                          ext.data_ptr(), lg, self._stream()))
-            net.agent_net = None
+        else:
+            for idx in sorted(self._nets):   # one launch per checkpoint, each over its own agents (CaNet.agent_net / net_index)
+                net = self._nets[idx][0]
+                net.agent_net, net.net_index = self._agent_net.data_ptr(), idx
+                nat.check(self.lib.cagpu_ga3c(C.byref(self.p), C.byref(self._cs), obs_ptr, C.byref(net),
+                                              ext.data_ptr(), lg, self._stream()))
+                net.agent_net = None
+        if sampler:
+            self._ga3c_sample(ext, lgt)
         return ext
 
-    def _ga3c_with_value(self, ext, obs_ptr, lg):
+    def _ga3c_with_value(self, ext, obs_ptr, lg, value=None):
         """ga3c() with the value head (load_ga3c(keep_value=True)): cagpu_ga3c_value instead of cagpu_ga3c, the same
-        launches otherwise; every checkpoint writes the value of its own agents into ga3c_value"""
+        launches otherwise; every checkpoint writes the value of its own agents into ga3c_value (or `value`)"""
+        value = self.ga3c_value if value is None else value
+
         def launch(net, ts):
             if "value_kernel" not in ts:
                 raise ValueError("ga3c_value is kept, but a loaded GA3C-CADRL checkpoint has no value head")
             v = nat.CaNetValue(value_kernel=ts["value_kernel"].data_ptr(), value_bias=ts["value_bias"].data_ptr(),
-                               value=self.ga3c_value.data_ptr())
+                               value=value.data_ptr())
             nat.check(self.lib.cagpu_ga3c_value(C.byref(self.p), C.byref(self._cs), obs_ptr, C.byref(net), ext.data_ptr(), lg,
                                                 C.byref(v), self._stream()))
         if self._agent_net is None:
@@ -528,6 +548,176 @@ class BatchedSim(object):
             finally:
                 net.agent_net = None
         return ext
+
+    # ---------------------------------------------------------------- the sampled policy and the experience tape
+    def set_ga3c_sampling(self, seed, temperature=1.0, mask=None, _address=None):
+        """GA3C-CADRL agents SAMPLE their action from the softmax of the logits (CaGa3cSample of include/cagpu.h states the
+        rule) instead of playing the argmax: a launch of its own behind the network launch of every ga3c() call.  Every draw
+        is a pure function of (seed, global env id, episode, agent slot, episode step) and the logits row, so step(),
+        collect(), every shard layout and replay() see the same numbers.  seed: an int != 0 that differs from the table's
+        heading_seed, the policy draw's seed, the map set's map_seed and the RVO draw's seed; None: switched off (greedy).
+        temperature > 0 divides the logits.  mask: bool broadcastable to [E, N], the agents that sample (None: every
+        GA3C-CADRL agent); the others keep the argmax.  ga3c_logp / ga3c_entropy / ga3c_action [E, N] then hold the last
+        step's log-probability of the index played, the entropy and the index, for the agents that were evaluated."""
+        self.sync()
+        if seed is None:
+            self._samp = None
+            return
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        taken = [0]
+        if self._ar is not None:
+            taken.append(int(self._ar.heading_seed))
+        if self._draw is not None:
+            taken.append(int(self._draw["c"].seed))
+        if self._maps is not None:
+            taken.append(int(self._maps.map_seed))
+        if self._rd is not None:
+            taken.append(int(self._rd["c"].seed))
+        if seed in taken:
+            raise ValueError("set_ga3c_sampling: seed must be != 0 and differ from the table's heading_seed, the policy draw's "
+                             "seed, the map set's map_seed and the RVO draw's seed")
+        if not (float(temperature) > 0 and math.isfinite(float(temperature))):
+            raise ValueError("set_ga3c_sampling: temperature must be > 0 and finite")
+        m = None
+        if mask is not None:
+            m = torch.from_numpy(np.array(np.broadcast_to(np.asarray(mask, bool), (self.E, self.N))).astype(np.uint8)) \
+                .to(self.device).contiguous()
+        addr = None if _address is None else self._dev(np.ascontiguousarray(_address, np.int64).reshape(self.E, 2), torch.int64)
+        self._samp = dict(seed=seed, temperature=float(temperature), mask=m, addr=addr)
+
+    def _sample_buffers(self):
+        if self.ga3c_logp is None:
+            z = lambda dt: torch.zeros((self.E, self.N), dtype=dt, device=self.device)
+            self.ga3c_logp, self.ga3c_entropy, self.ga3c_action = z(torch.float32), z(torch.float32), z(torch.int8)
+
+    def _ga3c_sample(self, ext, logits):
+        """the sampler launch behind the network launch(es) of a ga3c() call: cagpu_ga3c_sample over every evaluated agent
+        (of whichever checkpoint), greedy without set_ga3c_sampling; with a tape slot (collect) its pre-step record"""
+        self._sample_buffers()
+        g, sm, xp = self._cg, self._samp, self._xp
+        g.greedy = 1 if sm is None else 0
+        g.seed = 0 if sm is None else sm["seed"]
+        g.temperature = 1.0 if sm is None else sm["temperature"]
+        g.mask = None if sm is None or sm["mask"] is None else sm["mask"].data_ptr()
+        g.address = None if sm is None or sm["addr"] is None else sm["addr"].data_ptr()
+        g.agent_net = None      # (one launch for the agents of every checkpoint: an assignment names loaded checkpoints only)
+        g.logits = logits.data_ptr()
+        g.entropy = self.ga3c_entropy.data_ptr()
+        g.obs = self._obs.data_ptr()
+        g.value = None if self.ga3c_value is None else self.ga3c_value.data_ptr()
+        if xp is None:
+            g.logp, g.action = self.ga3c_logp.data_ptr(), self.ga3c_action.data_ptr()
+            g.slot_obs = g.slot_value = g.slot_live = g.slot_address = None
+        else:
+            g.logp, g.action = xp["logp"], xp["action"]
+            g.slot_obs, g.slot_value, g.slot_live, g.slot_address = xp["obs"], xp["value"], xp["live"], xp["address"]
+        nat.check(self.lib.cagpu_ga3c_sample(self._p_ref, self._cs_ref, self._ar_ref,
+                                             None if self._draw is None else self._draw["ref"],
+                                             None if self._maps is None else C.byref(self._maps),
+                                             None if self._rd is None else self._rd["ref"],
+                                             C.byref(g), ext.data_ptr(), self._stream()))
+
+    def experience_step_bytes(self, keep_obs=True):
+        """bytes of one step of an experience tape: 14 per agent slot (action, logp, value, live, reward, done) + 17 per env
+        (game_over, address), + 4 (W - 1) per agent slot with the observation rows"""
+        return self.E * self.N * (14 + (4 * (self.W - 1) if keep_obs else 0)) + 17 * self.E
+
+    def collect(self, n, keep_obs=True):
+        """Play n steps and keep the on-policy record of the batch's GA3C-CADRL agents on the device -> Experience (device
+        tensors, slot t = step t of this call):
+          obs [n, E, N, W - 1] float32 (keep_obs): the row the network read -- the pre-step observation minus is_learning
+          action [n, E, N] int8, logp [n, E, N] float32: the index played and its log-probability
+          value [n, E, N] float32: the value head of the same forward pass
+          live [n, E, N] bool: the agent was evaluated in that step (a GA3C-CADRL agent that was not done); every field
+                               above is zero where it is False
+          reward [n, E, N] float32, done [n, E, N] bool, game_over [n, E] bool: what the step gave
+          last_value [E, N] float32: one more network launch with the value head on the observation after step n - 1 (zero
+                               for agents it did not evaluate); it samples nothing and advances nothing
+          address [n, E, 2] int64: (global env id, episode) of every env before the step
+        The pre-step fields are written by the sampler launch of every step (cagpu_ga3c_sample's slot pointers), the
+        post-step fields by the step kernel itself (CaOut points at the slot); no host synchronisation between the first
+        launch and the return.  Greedy without set_ga3c_sampling (logp of the argmax).  Needs load_ga3c(keep_value=True).
+        The tape counts against experience_max_bytes: a call that would exceed it raises CagpuError before anything is
+        launched."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("collect: n must be >= 1")
+        self.sync()
+        if self._la is not None:
+            raise nat.CagpuError("collect: switch the look-ahead ring off first (the network runs between the steps)")
+        if self._net is None or self.ga3c_value is None or not self._has_ga3c:
+            raise nat.CagpuError("collect: needs GA3C-CADRL agents and load_ga3c(keep_value=True) (env.keep_ga3c_value = True "
+                                 "in the env API)")
+        per = self.experience_step_bytes(keep_obs)
+        total = n * per + 4 * self.E * self.N
+        if total > self.experience_max_bytes:
+            raise nat.CagpuError("experience tape: %d steps of %d bytes do not fit experience_max_bytes = %d%s; no step was taken"
+                                 % (n, per, self.experience_max_bytes,
+                                    " -- keep_obs=False takes %d bytes per step" % self.experience_step_bytes(False)
+                                    if keep_obs else ""))
+        if self._traj_on and self._traj_fit() < n:
+            raise nat.CagpuError("collect: the trajectory tape holds %d more steps, %d were asked for; no step was taken"
+                                 % (self._traj_fit(), n))
+        E, N, dev = self.E, self.N, self.device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        t = dict(obs=z((n, E, N, self.W - 1), torch.float32) if keep_obs else None, action=z((n, E, N), torch.int8),
+                 logp=z((n, E, N), torch.float32), value=z((n, E, N), torch.float32), live=z((n, E, N), torch.uint8),
+                 reward=z((n, E, N), torch.float32), done=z((n, E, N), torch.uint8), game_over=z((n, E), torch.uint8),
+                 last_value=z((E, N), torch.float32), address=z((n, E, 2), torch.int64))
+        self._sample_buffers()
+        co = self._co
+        keep = (co.rewards, co.done, co.game_over, self.fresh_outputs)
+        self.fresh_outputs = False
+        # (slot addresses by arithmetic: nine tensor views per step would cost more host time than the sampler launch)
+        at = {k: (v.data_ptr(), v[0].numel() * v.element_size()) for k, v in t.items() if v is not None}
+        ptr = lambda name, i: at[name][0] + i * at[name][1] if name in at else None
+        try:
+            for i in range(n):
+                self._xp = {k: ptr(k, i) for k in ("obs", "action", "logp", "value", "live", "address")}
+                co.rewards, co.done, co.game_over = ptr("reward", i), ptr("done", i), ptr("game_over", i)
+                self.step()
+        finally:
+            self._xp = None
+            co.rewards, co.done, co.game_over, self.fresh_outputs = keep
+        # the sim's own outputs and last-step records follow the last slot
+        self._rewards.copy_(t["reward"][n - 1])
+        self._done.copy_(t["done"][n - 1])
+        self._game_over.copy_(t["game_over"][n - 1])
+        last_live = t["live"][n - 1] != 0
+        torch.where(last_live, t["logp"][n - 1], self.ga3c_logp, out=self.ga3c_logp)
+        torch.where(last_live, t["action"][n - 1], self.ga3c_action, out=self.ga3c_action)
+        # the value of the observation after the last step: the network alone, into the tape
+        if self._ga3c_ext2 is None:
+            self._ga3c_ext2 = torch.zeros((E, N, 2), dtype=torch.float64, device=dev)
+        fused = self.ga3c_fused and not (N > 32 or self.p.sort_mode == nat.SORT_TIME_TO_IMPACT or self._variants)
+        self._ga3c_with_value(self._ga3c_ext2, None if fused else self._obs.data_ptr(), None, value=t["last_value"])
+        return Experience(self, t)
+
+    def update_ga3c(self, tensors, index=0):
+        """New weights for a loaded GA3C-CADRL network without leaving the device: `tensors` is a dict of float32 tensors on
+        this sim's device under the checkpoint's own keys and shapes (lstm_kernel ... logits_p_kernel, logits_p_bias,
+        input_mean, input_std, and logits_v_kernel [256, 1] / logits_v_bias [1] for a network loaded with a value head); any
+        subset.  They are copied into the network's buffers IN PLACE (no reallocation, no host round trip) and the matrix
+        planes are packed again (cagpu_ga3c_pack).  ValueError, before anything is copied: an unknown key, a wrong shape,
+        dtype or device, or logits_v_* for a network without a value head."""
+        self.sync()
+        if int(index) not in self._nets:
+            raise nat.CagpuError("update_ga3c: no GA3C-CADRL checkpoint loaded at index %s" % index)
+        net, ts = self._nets[int(index)]
+        dst = {_GA3C_NAMES.get(f, f): (ts[f], _GA3C_SHAPES[f]) for f in nat.NET_FIELDS}
+        if "value_kernel" in ts:
+            dst["logits_v_kernel"], dst["logits_v_bias"] = (ts["value_kernel"], (256, 1)), (ts["value_bias"], (1,))
+        todo = []
+        for k, v in tensors.items():
+            if k not in dst:
+                raise ValueError("update_ga3c: unknown key %r (expected a subset of %s)" % (k, sorted(dst)))
+            d, shape = dst[k]
+            if not torch.is_tensor(v) or v.dtype != torch.float32 or v.device != d.device or tuple(v.shape) != tuple(shape):
+                raise ValueError("update_ga3c: %s must be a float32 tensor of shape %s on %s" % (k, tuple(shape), d.device))
+            todo.append((d, v))
+        for d, v in todo:
+            d.copy_(v.reshape(d.shape))
+        nat.check(self.lib.cagpu_ga3c_pack(C.byref(net), ts["packed"].data_ptr(), ts["packed"].numel(), self._stream()))
 
     def generate_cases(self, num_cases, seed, side_length=4.0, speed_bnds=(0.5, 2.0), radius_bnds=(0.2, 0.8),
                        return_status=False, num_agents=None, return_counts=False):
@@ -1857,6 +2047,11 @@ class BatchedSim(object):
             mask = None if self._rd["mask"] is None else self._rd["mask"].index_select(0, torch.as_tensor(env, device=dev)).cpu().numpy() != 0
             child.set_rvo_draw(heading_noise=mask, _address=np.stack([pl["global_env"], pl["episode"]], axis=1),
                                **self._rd["args"])
+        if self._samp is not None:   # the parent's sampled GA3C-CADRL policy under the episodes' own addresses
+            sm = self._samp
+            mask = None if sm["mask"] is None else sm["mask"].index_select(0, torch.as_tensor(env, device=dev)).cpu().numpy() != 0
+            child.set_ga3c_sampling(sm["seed"], sm["temperature"], mask=mask,
+                                    _address=np.stack([pl["global_env"], pl["episode"]], axis=1))
         child.keep_final(True)
         child.log_episodes(capacity=capacity)
         if record:
@@ -2195,6 +2390,33 @@ _GA3C_NAMES = {"logits_kernel": "logits_p_kernel", "logits_bias": "logits_p_bias
 _GA3C_SHAPES = {"lstm_kernel": (71, 256), "lstm_bias": (256,), "layer1_kernel": (68, 256), "layer1_bias": (256,),
                 "layer2_kernel": (256, 256), "layer2_bias": (256,), "fc1_kernel": (256, 256), "fc1_bias": (256,),
                 "logits_kernel": (256, 11), "logits_bias": (11,), "input_mean": (138,), "input_std": (138,)}
+
+
+class Experience(object):
+    """What BatchedSim.collect(n) recorded (its docstring lists the fields: obs, action, logp, value, live, reward, done,
+    game_over, last_value, address -- device tensors, `n` steps); gae() adds advantages and returns."""
+    FIELDS = ("obs", "action", "logp", "value", "live", "reward", "done", "game_over", "last_value", "address")
+
+    def __init__(self, sim, t):
+        self._sim, self.n = sim, int(t["action"].shape[0])
+        for k in self.FIELDS:
+            v = t[k]
+            setattr(self, k, v.view(torch.bool) if v is not None and v.dtype == torch.uint8 else v)
+
+    def gae(self, gamma=0.99, lam=0.95):
+        """-> (advantage, returns), float32 [n, E, N], by cagpu_gae (include/cagpu.h has the rule: float32, every product and
+        sum rounded on its own).  Every ending is TERMINAL: where done[t] or game_over[t] is set the agent's episode ended
+        in step t and nothing is bootstrapped -- a time-out included, because the network is never queried on a terminal
+        observation.  Slots that are not live get 0 and cut the recursion; the last live slot of a column bootstraps from
+        last_value."""
+        sim = self._sim
+        n, E, N = self.reward.shape
+        adv, ret = torch.empty_like(self.reward), torch.empty_like(self.reward)
+        u8 = lambda v: v.view(torch.uint8).data_ptr()
+        nat.check(sim.lib.cagpu_gae(n, E * N, N, self.reward.data_ptr(), self.value.data_ptr(), self.last_value.data_ptr(),
+                                    u8(self.live), u8(self.done), u8(self.game_over), float(gamma), float(lam),
+                                    adv.data_ptr(), ret.data_ptr(), sim._stream()))
+        return adv, ret
 
 
 def _ga3c_weight_tensors(weights, device):

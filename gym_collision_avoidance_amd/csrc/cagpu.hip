@@ -776,6 +776,7 @@ __device__ __forceinline__ void reset_lane(Lane& r, const double* c, const bool 
 #include "cagpu_rules.inc"
 #include "cagpu_replay.inc"
 #include "cagpu_poses.inc"
+#include "cagpu_sample.inc"  // the sampled GA3C-CADRL policy, the experience tape's pre-step record, GAE
 
 // MSET: the n-step form (MULTI) also runs the map-set code of the single-step form -- the per-env grid of A3, the map draw
 // of an auto-reset.  A template flag that only a set launch with n_steps > 1 selects (main_variant in cagpu_launch.inc): every other

@@ -262,6 +262,78 @@ int cagpu_rvo_draw_at(const CaRvoDraw* rd, int32_t num_agents, const int64_t* g,
   return launch(rvo_draw_at_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), q);
 }
 
+int cagpu_ga3c_sample(const CaParams* p, const CaState* s, const CaAutoReset* ar, const CaPolicyDraw* draw, const CaMapSet* set,
+                      const CaRvoDraw* rd, const CaGa3cSample* g, double* ext_actions, void* stream) {
+  if (!p || !s || !g || !ext_actions || !g->logits || !g->logp || !s->flags || !s->step_num || !s->reset_count)
+    return fail(CA_EINVAL, "cagpu_ga3c_sample: NULL pointer (p, s, g, ext_actions, logits, logp, flags, step_num, reset_count)%s");
+  if (p->num_envs < 1 || p->num_agents < 1 || p->num_agents > big::NT_MAX || p->max_obs < 0)
+    return fail(CA_EINVAL, "cagpu_ga3c_sample: bad sizes (num_agents outside 1..1024)%s");
+  if (!g->greedy) {
+    if (g->seed == 0) return fail(CA_EINVAL, "cagpu_ga3c_sample: CaGa3cSample.seed must not be 0%s");
+    if ((ar && g->seed == ar->heading_seed) || (draw && g->seed == draw->seed) || (set && g->seed == set->map_seed) ||
+        (rd && g->seed == rd->seed))
+      return fail(CA_EINVAL, "cagpu_ga3c_sample: CaGa3cSample.seed equals CaAutoReset.heading_seed, CaPolicyDraw.seed, CaMapSet.map_seed "
+                             "or CaRvoDraw.seed (two rules would read the same uniforms)%s");
+  }
+  if (!(g->temperature > 0.0f) || !(g->temperature < INFINITY))
+    return fail(CA_EINVAL, "cagpu_ga3c_sample: CaGa3cSample.temperature must be > 0 and finite%s");
+  if (reinterpret_cast<uintptr_t>(g->address) & 7u) return fail(CA_EINVAL, "cagpu_ga3c_sample: CaGa3cSample.address must be 8-byte aligned%s");
+  if ((g->slot_obs && !g->obs) || (g->slot_value && !g->value))
+    return fail(CA_EINVAL, "cagpu_ga3c_sample: slot_obs needs obs and slot_value needs value%s");
+  sample::Args k;
+  std::memset(&k, 0, sizeof(k));
+  k.seed = g->greedy ? 0ull : g->seed;
+  k.inv_T = 1.0f / g->temperature;
+  k.greedy = g->greedy;
+  k.mask = g->mask; k.agent_net = g->agent_net; k.net_index = g->net_index; k.address = g->address;
+  k.logits = g->logits; k.flags = s->flags; k.step_num = s->step_num; k.reset_count = s->reset_count;
+  k.env_id_offset = ar ? static_cast<long>(ar->env_id_offset) : 0;
+  k.B = static_cast<long>(p->num_envs) * p->num_agents;
+  k.N = p->num_agents; k.W = 6 + 7 * p->max_obs;
+  k.ext = ext_actions; k.logp = g->logp; k.entropy = g->entropy; k.action = g->action;
+  k.obs = g->obs; k.value = g->value;
+  k.slot_obs = g->slot_obs; k.slot_value = g->slot_value; k.slot_live = g->slot_live; k.slot_address = g->slot_address;
+  const unsigned grid = static_cast<unsigned>((k.B + sample::NT - 1) / sample::NT);
+  return launch(sample::sample_kernel, dim3(grid), dim3(sample::NT), 0, static_cast<hipStream_t>(stream), k);
+}
+
+int cagpu_ga3c_sample_at(uint64_t seed, float temperature, int32_t num_agents, const int64_t* g, const int32_t* k, const int32_t* a,
+                         const int32_t* s, const float* logits, int64_t n, int8_t* action, float* logp, float* entropy,
+                         void* stream) {
+  if (!g || !k || !a || !s || !logits || (!action && !logp && !entropy) || num_agents < 1 || num_agents > big::NT_MAX || n < 0)
+    return fail(CA_EINVAL, "cagpu_ga3c_sample_at: NULL pointer, no output, num_agents outside 1..1024 or n < 0%s");
+  if (seed == 0) return fail(CA_EINVAL, "cagpu_ga3c_sample_at: seed must not be 0%s");
+  if (!(temperature > 0.0f) || !(temperature < INFINITY))
+    return fail(CA_EINVAL, "cagpu_ga3c_sample_at: temperature must be > 0 and finite%s");
+  if (n == 0) return CA_OK;
+  sample::AtArgs q;
+  std::memset(&q, 0, sizeof(q));
+  q.seed = seed; q.inv_T = 1.0f / temperature;
+  q.g = g; q.k = k; q.a = a; q.s = s; q.logits = logits; q.n = static_cast<long>(n);
+  q.action = action; q.logp = logp; q.entropy = entropy;
+  const unsigned grid = static_cast<unsigned>((n + sample::NT - 1) / sample::NT);
+  return launch(sample::sample_at_kernel, dim3(grid), dim3(sample::NT), 0, static_cast<hipStream_t>(stream), q);
+}
+
+int cagpu_gae(int32_t n, int64_t EN, int32_t num_agents, const float* reward, const float* value, const float* last_value,
+              const uint8_t* live, const uint8_t* done, const uint8_t* game_over, float gamma, float lambda, float* adv, float* ret,
+              void* stream) {
+  if (!reward || !value || !last_value || !live || !done || !game_over || !adv || !ret)
+    return fail(CA_EINVAL, "cagpu_gae: NULL pointer%s");
+  if (n < 1 || EN < 1 || num_agents < 1 || EN % num_agents != 0)
+    return fail(CA_EINVAL, "cagpu_gae: n < 1, EN < 1 or EN not a multiple of num_agents%s");
+  if (!(gamma >= 0.0f && gamma <= 1.0f) || !(lambda >= 0.0f && lambda <= 1.0f))
+    return fail(CA_EINVAL, "cagpu_gae: gamma and lambda must lie in [0, 1]%s");
+  sample::GaeArgs q;
+  std::memset(&q, 0, sizeof(q));
+  q.n = n; q.EN = static_cast<long>(EN); q.N = num_agents;
+  q.reward = reward; q.value = value; q.last_value = last_value; q.live = live; q.done = done; q.game_over = game_over;
+  q.gamma = gamma; q.gl = gamma * lambda;
+  q.adv = adv; q.ret = ret;
+  const unsigned grid = static_cast<unsigned>((EN + sample::NT - 1) / sample::NT);
+  return launch(sample::gae_kernel, dim3(grid), dim3(sample::NT), 0, static_cast<hipStream_t>(stream), q);
+}
+
 int cagpu_map_draw(uint64_t seed, int32_t num_maps, const int64_t* env_ids, const int32_t* counts, int64_t n, int32_t* out,
                    void* stream) {
   if (!env_ids || !counts || !out || seed == 0 || num_maps < 1 || n < 0)

@@ -683,6 +683,7 @@ class CollisionAvoidanceEnv(Env):
                 sim.set_ga3c_assignment(assign)
             else:
                 sim.set_ga3c_assignment(None)
+            self._apply_ga3c_sampling(sim)
         for e, g in enumerate(groups if self._fixture is None else [agents0]):
             if per_env is None or per_env[e] is not None or e == 0:
                 for a_idx, agent in enumerate(g):
@@ -1291,6 +1292,47 @@ class CollisionAvoidanceEnv(Env):
         if seed is not None and (int(seed) & 0xFFFFFFFFFFFFFFFF) == 0:
             raise ValueError("draw_rvo_on_device: seed must be != 0")
         self._rvo_device_seed = None if seed is None else int(seed)
+
+    def sample_ga3c_on_device(self, seed, temperature=1.0, mask=None):
+        """Batched mode: GA3C-CADRL agents SAMPLE their action from the softmax of their logits on the device, as a pure
+        function of (seed, global env id, episode, agent, episode step) (core.BatchedSim.set_ga3c_sampling; include/cagpu.h
+        CaGa3cSample), instead of playing the argmax.  seed: an int != 0 (None: greedy again); temperature > 0; mask: bool
+        broadcastable to [num_envs, num_agents], the agents that sample (None: all).  Takes effect at once on a batch that
+        has been reset(), and at every later reset()."""
+        if seed is not None and (int(seed) & 0xFFFFFFFFFFFFFFFF) == 0:
+            raise ValueError("sample_ga3c_on_device: seed must be != 0")
+        self._ga3c_sampling = None if seed is None else dict(seed=int(seed), temperature=float(temperature), mask=mask)
+        if self._sim is not None:
+            self._apply_ga3c_sampling(self._sim)
+
+    def _apply_ga3c_sampling(self, sim):
+        samp = getattr(self, "_ga3c_sampling", None)
+        if samp is None:
+            sim.set_ga3c_sampling(None)
+        else:
+            sim.set_ga3c_sampling(**samp)
+
+    def collect_experience(self, n, keep_obs=True):
+        """Batched mode: play n steps with built-in policies only and return the on-policy record of the GA3C-CADRL agents
+        as device tensors (core.BatchedSim.collect -> core.Experience: obs, action, logp, value, live, reward, done,
+        game_over, last_value, address; Experience.gae(gamma, lam) gives advantages and returns).  Needs
+        env.keep_ga3c_value = True before reset().  No host synchronisation between the first launch and the return."""
+        if self._sim is None:
+            raise RuntimeError("call reset() before collect_experience()")
+        if self._host_policies or (self._host_by_env and any(self._host_by_env)):
+            raise RuntimeError("collect_experience: user Python policies are queried on the host, step by step")
+        sim = self._sim
+        sim.p.dt = self.dt_nominal
+        self._la_dt_ok = True
+        self.episode_step_number += int(n)
+        xp = sim.collect(n, keep_obs=keep_obs)
+        self._snap, self._obs_np, self._scan_np = None, None, None
+        if Config.USE_STATIC_MAP:   # (once, on the final state, as rollout() does)
+            if self._map_lazy:
+                self._map_stale = True
+            else:
+                self._map_sensors()
+        return xp
 
     def replay(self, env_ids, episodes, **kw):
         """Run episodes of the batch again from their address -- `env_ids` (this shard's env indices, as episode_log()

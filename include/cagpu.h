@@ -942,6 +942,99 @@ int cagpu_step_noise(const CaParams *p, const CaState *s, const CaOut *o, const 
 int cagpu_rvo_draw_at(const CaRvoDraw *rd, int32_t num_agents, const int64_t *g, const int32_t *k, const int32_t *a,
                       const int32_t *s, int64_t n, uint8_t *out_noncoop_draw, double *out_noise, void *stream);
 
+/* SAMPLED GA3C-CADRL POLICY (additive to v12): the action of a GA3C-CADRL agent drawn from the softmax of its logits as a
+ * pure function of (seed, global env id, episode, agent slot, episode step) and the logits row, with its log-probability and
+ * the row's entropy -- what an on-policy method needs beside the value head (cagpu_ga3c_value).  A launch of its own that
+ * runs AFTER cagpu_ga3c / cagpu_ga3c_value (which wrote `logits` and the argmax into ext_actions) and BEFORE the step; no
+ * network kernel and no step kernel is touched.
+ *
+ * Who is evaluated: exactly the agents the network launch evaluated -- present, not CA_DONE, policy CA_POL_GA3C_CADRL, and
+ *   with agent_net != NULL only those with agent_net[i] == net_index.  Entries of every other agent are left alone.
+ * Who samples: an evaluated agent whose byte in `mask` (device uint8 [E*N]) is set; mask == NULL: every evaluated agent;
+ *   greedy != 0: nobody (seed is then neither read nor checked).  A sampling agent's ext_actions[e, n, 0] is overwritten with
+ *   the sampled index (and [e, n, 1] with 0.0); every other evaluated agent plays the index it holds, the first maximum of
+ *   its row.
+ * Address (g, k, a, s): CaRvoDraw's, word for word -- g = env_id_offset + e with a CaAutoReset and e without one, k =
+ *   CaState.reset_count[e], `address` != NULL overrides both per env ((g, k) = (address[2e], address[2e + 1]): a replay's
+ *   child batch), a the agent slot, s the agent's CaState.step_num before the move, 0 <= s < 2^22; an evaluated agent that
+ *   samples at s >= 2^22 uses the low 22 bits and raises bit 4 of the fault word.
+ * Uniform: u = words 0, 1 of block B0 of that address (CaRvoDraw: counter (g lo, g hi, k, (s << 10) | a)) under the key
+ *   `seed`, 53 bits: ((w0 >> 5) * 2^26 + (w1 >> 6)) / 2^53.  seed != 0, and different from CaAutoReset.heading_seed,
+ *   CaPolicyDraw.seed, CaMapSet.map_seed and CaRvoDraw.seed of the structs passed along.
+ * Probabilities, float32, in index order j = 0 .. 10, every operation rounded on its own (no fused multiply-add):
+ *   inv_T = 1.0f / temperature (divided on the host);   m = max_j l_j;   z_j = (l_j - m) * inv_T;   q_j = expf(z_j);
+ *   c_j = c_(j-1) + q_j (c_-1 = 0);   S = c_10.
+ * Choice: the first j with (float)u * S < c_j, and 10 if there is none (np.random.choice's
+ *   searchsorted(cdf, u, side="right") without the division by S).
+ * Outputs, for EVERY evaluated agent, with i the index that is played (sampled, or held):
+ *   logp    = z_i - logf(S)
+ *   entropy = logf(S) - (sum_j q_j * z_j) / S       (products rounded, summed in index order, one correctly rounded divide)
+ *   action  = i as int8
+ * Bad rows: a row with a NaN logit plays index 0 if it samples (the held index otherwise), gets logp = entropy = NaN and
+ *   raises bit 5 of the fault word (cagpu_device_faults).
+ * expf / logf are the device libm's (<= 2 ulp): reproducible on the device (cagpu_ga3c_sample_at), to a few ulp elsewhere.
+ *
+ * The pre-step half of an experience tape slot (all four nullable, independent of each other), written by the same launch:
+ *   slot_obs     float32 [E, N, W - 1]  the row the network read (obs[e, n, 1:], W = 6 + 7 max_obs) of every evaluated agent
+ *   slot_value   float32 [E, N]         value[e, n] of every evaluated agent (`value`: what cagpu_ga3c_value wrote)
+ *   slot_live    uint8   [E, N]         1 for an evaluated agent, 0 for every other slot (written for ALL slots)
+ *   slot_address int64   [E, 2]         (g, k) of every env
+ * logp / entropy / action may point into a tape slot as well. */
+typedef struct CaGa3cSample {
+  uint64_t       seed;          /* != 0 and no other rule's seed (unless greedy) */
+  float          temperature;   /* > 0, finite */
+  int32_t        greedy;        /* != 0: nobody samples; the outputs are those of the held argmax */
+  const uint8_t *mask;          /* device [E*N] or NULL = every evaluated agent samples */
+  const int32_t *agent_net;     /* device [E*N] or NULL (CaNet.agent_net) */
+  int32_t        net_index;
+  int32_t        reserved0;
+  const int64_t *address;       /* device [2*E], 8-byte aligned, or NULL */
+  const float   *logits;        /* device [E,N,11]: what the network launch wrote */
+  float         *logp;          /* device [E,N] */
+  float         *entropy;       /* device [E,N] or NULL */
+  int8_t        *action;        /* device [E,N] or NULL */
+  const float   *obs;           /* device [E,N,W]: needed with slot_obs */
+  const float   *value;         /* device [E,N]: needed with slot_value */
+  float         *slot_obs;
+  float         *slot_value;
+  uint8_t       *slot_live;
+  int64_t       *slot_address;
+} CaGa3cSample;                 /* 128 bytes */
+
+/* CA_EINVAL, nothing launched: p, s, g, ext_actions, g->logits, g->logp or CaState.flags / step_num / reset_count NULL;
+ * num_agents outside 1..1024; without greedy a seed of 0 or one that equals ar->heading_seed, draw->seed, set->map_seed or
+ * rd->seed (ar, draw, set and rd may each be NULL: the call has no such rule); temperature not > 0 or not finite; address not
+ * 8-byte aligned; slot_obs without obs, slot_value without value.  Asynchronous on `stream`; cagpu_last_kernel() keeps
+ * naming the network launch. */
+int cagpu_ga3c_sample(const CaParams *p, const CaState *s, const CaAutoReset *ar, const struct CaPolicyDraw *draw,
+                      const CaMapSet *set, const CaRvoDraw *rd, const CaGa3cSample *g, double *ext_actions, void *stream);
+
+/* The rule above for n arbitrary (address, logits row) pairs, every row sampling, with no simulator: g / k / a / s device
+ * int64 / int32 / int32 / int32 [n], logits device float32 [n, 11]; action (int8), logp, entropy device [n], each may be
+ * NULL (not all three).  n == 0: nothing is launched.  CA_EINVAL, nothing launched: an input pointer NULL, no output, seed
+ * == 0, temperature not > 0 or not finite, num_agents outside 1..1024, n < 0. */
+int cagpu_ga3c_sample_at(uint64_t seed, float temperature, int32_t num_agents, const int64_t *g, const int32_t *k,
+                         const int32_t *a, const int32_t *s, const float *logits, int64_t n, int8_t *action, float *logp,
+                         float *entropy, void *stream);
+
+/* Generalised advantage estimation over an experience tape of n steps: reward, value float32 [n, EN]; live, done uint8
+ * [n, EN]; game_over uint8 [n, EN / num_agents]; last_value float32 [EN] (the value of the observation after step n - 1);
+ * adv, ret float32 [n, EN] (all device).  One lane per (env, agent) column i, float32, every product and sum rounded on
+ * its own, gl = gamma * lambda multiplied once on the host in float32:
+ *   carry = 0; nv = last_value[i]
+ *   for t = n - 1 .. 0:
+ *     if !live[t, i]:                        adv[t, i] = ret[t, i] = 0; carry = 0; nv = 0; continue
+ *     if done[t, i] | game_over[t, i / N]:   nv = 0; carry = 0        (the agent's episode ended in step t: terminal)
+ *     delta = (reward[t, i] + gamma * nv) - value[t, i]
+ *     carry = delta + gl * carry
+ *     adv[t, i] = carry; ret[t, i] = carry + value[t, i]; nv = value[t, i]
+ * Every ending is terminal, a time-out included: the network is never queried on a terminal observation, so there is
+ * nothing to bootstrap from.  CA_EINVAL, nothing launched: a NULL pointer, n < 1, EN < 1, EN not a multiple of num_agents,
+ * gamma or lambda outside [0, 1]. */
+int cagpu_gae(int32_t n, int64_t EN, int32_t num_agents, const float *reward, const float *value, const float *last_value,
+              const uint8_t *live, const uint8_t *done, const uint8_t *game_over, float gamma, float lambda, float *adv,
+              float *ret, void *stream);
+
 /* The policy query of the NEXT step ahead of time (collision_avoidance_env.py:305-323 for the built-in RVO policy):
  * fills s->next_action from the CURRENT state and sets CA_PLAN_VALID, without stepping.  cagpu_step / cagpu_rollout keep
  * the plan up to date by themselves; this entry point exists for states that did not come out of a step (the reset state
@@ -981,7 +1074,9 @@ uint64_t cagpu_workspace_bytes(const CaParams *p);
  * slot that still held an older episode, i.e. it REPEATED a scenario (valid memory, a valid case -- but not the stream's);
  * raised by cagpu_stream_refill's kernel.  A larger window, or shorter launches, avoid it.
  * bit 4 = an agent was queried under a CaRvoDraw at an episode step s >= 2^22, outside the draw's address rule (its draw
- * repeated the one of step s - 2^22).
+ * repeated the one of step s - 2^22); a sampling agent of a CaGa3cSample at such a step raises it as well.
+ * bit 5 = a logits row with a NaN reached cagpu_ga3c_sample / cagpu_ga3c_sample_at: its agent played index 0 (or kept the
+ * index it held) and its logp / entropy are NaN.
  * *faults receives the word; clear != 0 resets it.  0 in normal operation; check it wherever the host synchronises anyway. */
 int cagpu_device_faults(uint32_t *faults, int32_t clear);
 
