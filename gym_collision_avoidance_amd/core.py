@@ -2372,7 +2372,8 @@ class BatchedSim(object):
         if f:
             raise nat.CagpuError("device fault word 0x%x:%s%s%s%s the simulator state is not to be trusted" % (
                 f, " a hand-over inside the pipelined step kernel timed out;" if f & 1 else "",
-                " a GA3C-CADRL operand left the fp16 range of the network kernel's two-plane split (|x| >= 65504);" if f & 2 else "",
+                " a GA3C-CADRL operand left the fp16 range of the network kernel's two-plane split (|x| >= 65504, or an "
+                "input column was not finite);" if f & 2 else "",
                 " bit 2: a map-set env's map index (env_map) lay outside [0, num_maps), that env saw an empty map;" if f & 4 else "",
                 " bit 3: an env of a case stream auto-reset more than `window` times between two refills and repeated a "
                 "scenario (set_case_stream: a larger window, or shorter launches);" if f & 8 else ""))

@@ -531,7 +531,19 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
   // this thread-local maximum; a value at or beyond fp16's largest finite number would become +-inf in its high plane and
   // the network would answer from saturated operands WITHOUT any sign of it (ReLU swallows the NaNs that follow).  Checked
   // once at the kernel's end: bit 1 of the device's fault word (cagpu_device_faults).  ~160 v_max per thread and launch.
-  float amax = 0.f, amax_unused = 0.f;
+  // The INPUT columns -- the other-agent block and the four host columns, which reach layer1 unsplit -- may hold a NaN, and
+  // v_max_f32 returns its other operand then: the NaN would leave the maximum alone, ReLU would swallow it
+  // (fmaxf(NaN + b, 0) = 0) and the network would answer from zeros with the word clear.  Their maximum is therefore taken
+  // on the BIT PATTERNS of |x| as unsigned integers (absmax_bits): non-negative floats order like their patterns, +inf lies
+  // above every finite value and every NaN above +inf.  Behind the prologue it becomes the float maximum the activations
+  // continue (they are ReLU outputs: never NaN), +inf standing for "out of range" (sticky under v_max_f32).
+  constexpr unsigned int FP16_MAX_BITS = 0x477FE000u;  // 65 504.f
+  auto absmax_bits = [](const unsigned int mx, const float x) {
+    const unsigned int b = __builtin_bit_cast(unsigned int, x) & 0x7FFFFFFFu;
+    return b > mx ? b : mx;
+  };
+  unsigned int xmax = 0u;
+  float amax_unused = 0.f;
 
   // ---- X = obs[1:] zero-padded / cropped to 138 (GA3CCADRLPolicy.py:69-75, network.py:24-35); sub, div.
   // Four threads per row, 35 columns each; every global load is issued before the first use and none sits behind a
@@ -644,7 +656,7 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
       for (int f = 0; f < 7; ++f) {
         const int c = 5 + 7 * slot + f;
         const float xn = (v7[f] - g.net.input_mean[c]) / g.net.input_std[c];
-        amax = fmaxf(amax, fabsf(xn));
+        xmax = absmax_bits(xmax, xn);
         xo[rr * XO_LD + c - 5] = xn;
       }
     }
@@ -658,7 +670,11 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
       const float h4[4] = {here ? static_cast<float>(eg.dist) : 0.f, here ? static_cast<float>(eg.heading_ego) : 0.f,
                            here ? static_cast<float>(hps) : 0.f, row_ok ? static_cast<float>(hr) : 0.f};
 #pragma unroll
-      for (int c = 1; c < 5; ++c) hostv[rr * 4 + c - 1] = (h4[c - 1] - g.net.input_mean[c]) / g.net.input_std[c];
+      for (int c = 1; c < 5; ++c) {
+        const float xn = (h4[c - 1] - g.net.input_mean[c]) / g.net.input_std[c];
+        xmax = absmax_bits(xmax, xn);
+        hostv[rr * 4 + c - 1] = xn;
+      }
     }
     __syncthreads();
     // give the scratch back (zeros, as the LSTM expects)
@@ -701,13 +717,15 @@ __global__ __launch_bounds__(NT, 2) void ga3c_kernel(const Args g, const typenam
         atomicMax(&misc[1], sl);
         if (row_ok) atomicMin(&misc[2], sl);
       } else if (c < 5) {
+        xmax = absmax_bits(xmax, xn);
         hostv[rr * 4 + c - 1] = xn;  // strided_slice_1
       } else if (c < XIN) {
-        amax = fmaxf(amax, fabsf(xn));
+        xmax = absmax_bits(xmax, xn);
         xo[rr * XO_LD + c - 5] = xn;  // strided_slice_2
       }
     }
   }
+  float amax = xmax < FP16_MAX_BITS ? __builtin_bit_cast(float, xmax) : __builtin_inff();  // (see the guard above)
 
   // ---- this wave's LSTM weights: gate g4 (i, j, f, o), units 16 wv .. 16 wv + 15 = packed column block 4 g4 + wv.
   // h part: two planes x two k-blocks per gate.  x part (rows 0..6 of the kernel) + bias: the float32 MFMA is NOT used --

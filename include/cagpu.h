@@ -1066,8 +1066,11 @@ uint64_t cagpu_workspace_bytes(const CaParams *p);
 /* Device-side fault word of the CURRENT device (synchronises it): bit 0 = a bounded hand-over poll inside the pipelined
  * step kernel ran out (csrc/cagpu_pipe.inc wait_for), i.e. some launch since the last clear may have produced wrong state.
  * bit 1 = an operand of the GA3C-CADRL network kernel left the range of its two-plane fp16 split (|x| >= 65504: a normalised
- * input or an activation; csrc/cagpu_ga3c.inc), i.e. some cagpu_ga3c call since the last clear chose its actions from
- * saturated values.
+ * input or an activation; csrc/cagpu_ga3c.inc), or an input column the network reads -- the four host columns and the
+ * 19 x 7 other-agent block, after the normalisation -- was not finite (+-inf or NaN: ReLU would swallow the NaN and the
+ * network would answer from zeros), i.e. some cagpu_ga3c / cagpu_ga3c_value / cagpu_ga3c_query call since the last clear
+ * chose its actions from saturated or missing values.  Healthy up to the bound: a normalised input of +-65 503.99 leaves
+ * the word clear and the logits within the tests' bar of a float64 evaluation (tests/test_gpu_ga3c_edges.py).
  * bit 2 = a map-set env's map index (CaMapSet.env_map) lay outside [0, num_maps) (cagpu_step_maps / cagpu_laserscan_maps /
  * cagpu_occupancy_grid_maps, v12): that env saw an empty map in some call since the last clear.
  * bit 3 = an env of a case stream (CaCaseStream) auto-reset more than `window` times between two refills: it loaded a window

@@ -716,28 +716,7 @@ def test_ga3c_balanced_tile_heights_cover_every_row(live_rows):
     assert np.array_equal(g.ga3c_logits.cpu().numpy(), got) and np.array_equal(ext2.cpu().numpy(), ex)
 
 
-def _ga3c_logits_f64(w, x):
-    """the graph of oracle/ga3c_ref.GA3CNet.logits evaluated in float64 (normalisation in float32 like the graph: it is
-    the network's INPUT): the yardstick for what a float32 evaluation -- numpy's or the kernel's -- loses"""
-    x = np.asarray(x, dtype=np.float32)
-    B = x.shape[0]
-    seq = x[:, 0].astype(np.int32)
-    xn = ((x - w["input_mean"]) / w["input_std"]).astype(np.float32).astype(np.float64)
-    host, others = xn[:, 1:5], xn[:, 5:].reshape(B, 19, 7)
-    W = {k: v.astype(np.float64) for k, v in w.items()}
-    sg = lambda v: 1.0 / (1.0 + np.exp(-v))
-    h, c = np.zeros((B, 64)), np.zeros((B, 64))
-    for t in range(19):
-        z = np.concatenate([others[:, t], h], axis=1) @ W["lstm_kernel"] + W["lstm_bias"]
-        i, j, f, o = np.split(z, 4, axis=1)
-        cn = sg(f + 1.0) * c + sg(i) * np.tanh(j)
-        hn = sg(o) * np.tanh(cn)
-        live = (t < seq)[:, None]
-        c, h = np.where(live, cn, c), np.where(live, hn, h)
-    a = np.concatenate([host, h], axis=1)
-    for n in ("layer1", "layer2", "fc1"):
-        a = np.maximum(a @ W[n + "_kernel"] + W[n + "_bias"], 0)
-    return a @ W["logits_p_kernel"] + W["logits_p_bias"]
+from tests.ga3c_f64_ref import logits_f64 as _ga3c_logits_f64  # noqa: E402  (the float64 yardstick, shared with tests/test_gpu_ga3c_edges.py)
 
 
 def test_ga3c_split_operand_network_is_float32_accurate():
