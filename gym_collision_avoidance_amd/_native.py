@@ -176,6 +176,13 @@ class CaNetValue(C.Structure):
     _fields_ = [("value_kernel", _P), ("value_bias", _P), ("value", _P)]
 
 
+class CaNetGrad(C.Structure):
+    """one call of the network's backward pass (cagpu_ga3c_grad); include/cagpu.h states the rule and grad's layout"""
+    _fields_ = [("x", _P), ("rows", C.c_int64), ("width", C.c_int32), ("accumulate", C.c_int32), ("live", _P),
+                ("dlogits", _P), ("dvalue", _P), ("value_kernel", _P), ("value_bias", _P), ("grad", _P), ("work", _P),
+                ("work_bytes", C.c_uint64)]
+
+
 EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_reset", "cagpu_step", "cagpu_step_map", "cagpu_rollout",
            "cagpu_orca", "cagpu_observe", "cagpu_laserscan", "cagpu_ga3c", "cagpu_generate_cases", "cagpu_generate_cases_ragged", "cagpu_plan", "cagpu_debug_libm", "cagpu_device_faults", "cagpu_workspace_bytes",
            "cagpu_ga3c_packed_bytes", "cagpu_ga3c_pack", "cagpu_rollout_ring", "cagpu_ring_snapshots", "cagpu_debug_copy8", "cagpu_device_faults_async",
@@ -186,7 +193,8 @@ EXPORTS = ("cagpu_version", "cagpu_last_error", "cagpu_last_kernel", "cagpu_rese
            "cagpu_generate_cases_at", "cagpu_stream_refill", "cagpu_episode_metrics_carry_bytes", "cagpu_episode_metrics",
            "cagpu_step_ex_maps", "cagpu_map_draw", "cagpu_heading_draw", "cagpu_policy_draw_at", "cagpu_step_tape",
            "cagpu_tape_poses", "cagpu_laserscan_slots", "cagpu_laserscan_history", "cagpu_step_noise", "cagpu_rvo_draw_at",
-           "cagpu_ga3c_sample", "cagpu_ga3c_sample_at", "cagpu_gae")
+           "cagpu_ga3c_sample", "cagpu_ga3c_sample_at", "cagpu_gae",
+           "cagpu_ga3c_grad_floats", "cagpu_ga3c_grad_work_bytes", "cagpu_ga3c_grad")
 
 _lib = None
 
@@ -280,10 +288,16 @@ def lib():
     L.cagpu_ga3c_packed_bytes.restype = C.c_uint64
     L.cagpu_ga3c_pack.argtypes = [C.POINTER(CaNet), _P, C.c_uint64, _P]
     L.cagpu_debug_libm.argtypes = [C.c_int32, C.c_int32, _P, _P, _P, _P]
+    L.cagpu_ga3c_grad_floats.argtypes = []
+    L.cagpu_ga3c_grad_floats.restype = C.c_uint64
+    L.cagpu_ga3c_grad_work_bytes.argtypes = [C.c_int64]
+    L.cagpu_ga3c_grad_work_bytes.restype = C.c_uint64
+    L.cagpu_ga3c_grad.argtypes = [C.POINTER(CaNet), C.POINTER(CaNetGrad), _P]
     for n in EXPORTS:
         getattr(L, n)  # AttributeError if a declared symbol is missing
         if n not in ("cagpu_last_error", "cagpu_last_kernel", "cagpu_workspace_bytes", "cagpu_ga3c_packed_bytes",
-                     "cagpu_render_work_bytes", "cagpu_episode_metrics_carry_bytes"):
+                     "cagpu_render_work_bytes", "cagpu_episode_metrics_carry_bytes", "cagpu_ga3c_grad_floats",
+                     "cagpu_ga3c_grad_work_bytes"):
             getattr(L, n).restype = C.c_int
     L.cagpu_last_error.restype = C.c_char_p
     L.cagpu_last_kernel.restype = C.c_char_p

@@ -2419,6 +2419,15 @@ class Experience(object):
                                     adv.data_ptr(), ret.data_ptr(), sim._stream()))
         return adv, ret
 
+    def rows(self):
+        """-> (x [n E N, W - 1] float32, live [n E N] bool): every (step, env, agent) slot of the tape as one row, in that
+        order -- VIEWS of the tape, no boolean selection and therefore no host synchronisation (what
+        experiments/collect_onpolicy.collect pays for its compact batch).  ga3c_grad and ga3c_train.TrainableGA3C take the
+        pair as it is: rows that are not live are never read."""
+        if self.obs is None:
+            raise nat.CagpuError("Experience.rows: the tape was collected with keep_obs=False")
+        return self.obs.reshape(-1, self.obs.shape[-1]), self.live.reshape(-1)
+
 
 def _ga3c_weight_tensors(weights, device):
     """weights (None = the shipped default, an .npz path, or a dict of float32 arrays) -> {CaNet field: device tensor},
@@ -2520,6 +2529,136 @@ def ga3c_query(x, weights=None, want=("logits", "value", "action"), device=None)
         st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         nat.check(nat.lib().cagpu_ga3c_query(C.byref(net), C.byref(q), st))
     return out
+
+
+# ---------------------------------------------------------------- the network's weight gradients (cagpu_ga3c_grad)
+# the layout of the flat gradient: the checkpoint's key order and shapes (include/cagpu.h, CaNetGrad)
+GA3C_GRAD_LAYOUT = (("lstm_kernel", (71, 256)), ("lstm_bias", (256,)), ("layer1_kernel", (68, 256)), ("layer1_bias", (256,)),
+                    ("layer2_kernel", (256, 256)), ("layer2_bias", (256,)), ("fc1_kernel", (256, 256)), ("fc1_bias", (256,)),
+                    ("logits_p_kernel", (256, 11)), ("logits_p_bias", (11,)), ("logits_v_kernel", (256, 1)),
+                    ("logits_v_bias", (1,)))
+
+
+def ga3c_grad_offsets():
+    """-> {checkpoint key: (offset in floats, shape)} of cagpu_ga3c_grad's flat gradient, and their total as [None]"""
+    out, at = {}, 0
+    for k, shape in GA3C_GRAD_LAYOUT:
+        out[k] = (at, shape)
+        at += int(np.prod(shape))
+    out[None] = (at, ())
+    return out
+
+
+def ga3c_grad_views(flat):
+    """the flat gradient buffer -> {checkpoint key: view of its own shape}"""
+    return {k: flat[o:o + int(np.prod(s))].view(s) for k, (o, s) in ga3c_grad_offsets().items() if k is not None}
+
+
+def ga3c_grad_chunk_rows(rows, max_work_bytes, work_bytes=None):
+    """rows per cagpu_ga3c_grad call such that its workspace stays within max_work_bytes: a pure function of the two.  All
+    rows where they fit; else the rows are cut into the fewest chunks that fit, of equal size (the last may be shorter).
+    work_bytes: rows -> bytes (default: cagpu_ga3c_grad_work_bytes).  ValueError if not even one row fits."""
+    wb = work_bytes if work_bytes is not None else (lambda r: int(nat.lib().cagpu_ga3c_grad_work_bytes(int(r))))
+    rows, budget = int(rows), int(max_work_bytes)
+    if rows <= 0 or wb(rows) <= budget:
+        return max(rows, 0)
+    if wb(1) > budget:
+        raise ValueError("ga3c_grad: max_work_bytes = %d is below the workspace of a single row (%d bytes)" % (budget, wb(1)))
+    lo, hi = 1, rows          # wb(lo) <= budget < wb(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if wb(mid) <= budget:
+            lo = mid
+        else:
+            hi = mid
+    chunks = -(-rows // lo)
+    return -(-rows // chunks)
+
+
+def _grad_net(weights, device):
+    """weights as ga3c_query takes them, or a dict of float32 device tensors under the checkpoint's keys ->
+    (CaNet, value_kernel tensor or None, value_bias tensor or None, what keeps the memory alive)"""
+    if isinstance(weights, dict) and weights and all(torch.is_tensor(v) for v in weights.values()):
+        shapes = dict(GA3C_GRAD_LAYOUT, input_mean=(138,), input_std=(138,))
+        ts = {}
+        for k, v in weights.items():
+            if k not in shapes:
+                raise ValueError("ga3c_grad: unknown weight key %r" % (k,))
+            if v.dtype != torch.float32 or v.device != device or tuple(v.shape) != shapes[k]:
+                raise ValueError("ga3c_grad: %s must be a float32 tensor of shape %s on %s" % (k, shapes[k], device))
+            ts[k] = v.detach().contiguous()
+        missing = [_GA3C_NAMES.get(f, f) for f in nat.NET_FIELDS if _GA3C_NAMES.get(f, f) not in ts]
+        if missing:
+            raise ValueError("ga3c_grad: weights lack %s" % ", ".join(missing))
+        net = nat.CaNet(**{f: ts[_GA3C_NAMES.get(f, f)].data_ptr() for f in nat.NET_FIELDS})
+        return net, ts.get("logits_v_kernel"), ts.get("logits_v_bias"), ts
+    net, ts, _ = _query_net(weights, device)
+    return net, ts.get("value_kernel"), ts.get("value_bias"), ts
+
+
+def _ga3c_grad_into(flat, net, value_kernel, value_bias, xt, dlogits, dvalue, live, max_work_bytes):
+    """cagpu_ga3c_grad into the flat buffer, chunked in array order under the workspace budget (accumulate from the second
+    chunk on).  Every tensor is a contiguous device tensor of the right dtype (or None) by now."""
+    L = nat.lib()
+    rows, width = int(xt.shape[0]), int(xt.shape[1])
+    if rows == 0:
+        flat.zero_()
+        return flat
+    chunk = ga3c_grad_chunk_rows(rows, max_work_bytes)
+    work = torch.empty((int(L.cagpu_ga3c_grad_work_bytes(chunk)),), dtype=torch.uint8, device=xt.device)
+    at = lambda t, r0, per: None if t is None else t.data_ptr() + r0 * per * t.element_size()
+    with torch.cuda.device(xt.device):
+        st = C.c_void_p(torch.cuda.current_stream(xt.device).cuda_stream)
+        for r0 in range(0, rows, chunk):
+            q = nat.CaNetGrad(x=at(xt, r0, width), rows=min(chunk, rows - r0), width=width, accumulate=1 if r0 else 0,
+                              live=at(live, r0, 1), dlogits=at(dlogits, r0, 11), dvalue=at(dvalue, r0, 1),
+                              value_kernel=None if value_kernel is None else value_kernel.data_ptr(),
+                              value_bias=None if value_bias is None else value_bias.data_ptr(),
+                              grad=flat.data_ptr(), work=work.data_ptr(), work_bytes=work.numel())
+            nat.check(L.cagpu_ga3c_grad(C.byref(net), C.byref(q), st))
+    return flat
+
+
+def ga3c_grad(x, dlogits=None, dvalue=None, live=None, weights=None, max_work_bytes=256 << 20):
+    """Weight gradients of the GA3C-CADRL network (cagpu_ga3c_grad; include/cagpu.h states the rule): the SUM over the live
+    rows of the row's vector-Jacobian product with the upstream gradients dlogits [rows, 11] (of logits_p) and dvalue [rows]
+    (of the value head); at least one of the two.  x: [rows, width] as ga3c_query takes it; live: bool / uint8 [rows] or
+    None -- rows with live == 0 are never read.  weights: as ga3c_query, or a dict of float32 device tensors under the
+    checkpoint's keys (a learner's current parameters).  -> {checkpoint key: float32 device tensor}, views of ONE flat
+    buffer in the order of GA3C_GRAD_LAYOUT (what an all-reduce would take).  The workspace of a call holds ~36 KB per row:
+    where it would exceed max_work_bytes the rows are chunked in array order (ga3c_grad_chunk_rows) and accumulated.
+    Deterministic: the same inputs and budget give the same bytes."""
+    if dlogits is None and dvalue is None:
+        raise ValueError("ga3c_grad: give dlogits, dvalue or both")
+    device = x.device if (torch.is_tensor(x) and x.is_cuda) else torch.device("cuda:0")
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    xt = torch.as_tensor(x)
+    if xt.dim() != 2 or xt.shape[1] < 1:
+        raise ValueError("ga3c_grad: x must be [rows, width >= 1], got shape %s" % (tuple(xt.shape),))
+    xt = xt.to(device=device, dtype=torch.float32).contiguous()
+    rows = int(xt.shape[0])
+
+    def up(t, shape, name, dtype=torch.float32):
+        if t is None:
+            return None
+        t = torch.as_tensor(t)
+        if t.dtype == torch.bool:
+            t = t.to(torch.uint8) if not t.is_cuda else t.contiguous().view(torch.uint8)
+        t = t.to(device=device, dtype=dtype).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError("ga3c_grad: %s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+        return t
+    dl, dv = up(dlogits, (rows, 11), "dlogits"), up(dvalue, (rows,), "dvalue")
+    lv = up(live, (rows,), "live", torch.uint8)
+    net, vk, vb, keep = _grad_net(weights, device)
+    if dv is not None and vk is None:
+        raise ValueError("ga3c_grad: dvalue given, but these GA3C-CADRL weights have no logits_v_kernel / logits_v_bias")
+    flat = torch.empty((ga3c_grad_offsets()[None][0],), dtype=torch.float32, device=device)
+    _ga3c_grad_into(flat, net, vk, vb, xt, dl, dv, lv, max_work_bytes)
+    del keep
+    return ga3c_grad_views(flat)
 
 
 def orca(pos, vel, pref, radius, max_speed, collab=0.5, time_horizon=5.0, time_step=0.1, max_neighbors=None,

@@ -628,6 +628,7 @@ __host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~static_
 #include "cagpu_render.inc"
 #include "cagpu_metrics.inc"
 #include "cagpu_ga3c.inc"
+#include "cagpu_ga3c_grad.inc"  // the network's weight gradients (cagpu_ga3c_grad)
 #include "cagpu_gen.inc"
 
 // The map a map-set env takes at its k-th auto-reset (CaMapSet.map_seed): min(floor(M u), M - 1), u the Philox uniform of

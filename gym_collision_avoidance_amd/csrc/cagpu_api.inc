@@ -697,6 +697,69 @@ int cagpu_ga3c_query(const CaNet* net, const CaNetQuery* q, void* stream) {
   return ga3c_launch_ext(k, ex, stream);
 }
 
+// ---- the weight gradients of the GA3C-CADRL network (csrc/cagpu_ga3c_grad.inc)
+uint64_t cagpu_ga3c_grad_floats(void) { return static_cast<uint64_t>(ga3c_grad::G_TOTAL); }
+
+uint64_t cagpu_ga3c_grad_work_bytes(int64_t rows) {
+  if (rows <= 0 || rows >= (1LL << 31)) return 0;  // (rows == 0: the call launches nothing and needs no workspace)
+  return static_cast<uint64_t>(ga3c_grad::layout_of(static_cast<long>(rows)).total) * sizeof(float);
+}
+
+int cagpu_ga3c_grad(const CaNet* net, const CaNetGrad* q, void* stream) {
+  namespace gg = ga3c_grad;
+  if (!net || !q || !q->grad) return fail(CA_EINVAL, "cagpu_ga3c_grad: NULL argument (net, g or grad)%s");
+  if (q->rows != 0 && (!q->x || !q->work)) return fail(CA_EINVAL, "cagpu_ga3c_grad: NULL x or work%s");
+  if (q->rows < 0 || q->width < 1) return fail(CA_EINVAL, "cagpu_ga3c_grad: rows must be >= 0 and width >= 1%s");
+  if (!q->dlogits && !q->dvalue) return fail(CA_EINVAL, "cagpu_ga3c_grad: dlogits and dvalue are both NULL%s");
+  if (q->dvalue && (!q->value_kernel || !q->value_bias))
+    return fail(CA_EINVAL, "cagpu_ga3c_grad: dvalue needs value_kernel and value_bias (logits_v)%s");
+  const void* w[] = {net->lstm_kernel, net->lstm_bias, net->layer1_kernel, net->layer1_bias, net->layer2_kernel, net->layer2_bias,
+                     net->fc1_kernel, net->fc1_bias, net->logits_kernel, net->logits_bias, net->input_mean, net->input_std};
+  for (const void* p : w)
+    if (!p) return fail(CA_EINVAL, "cagpu_ga3c_grad: NULL weight pointer%s");
+  if (q->rows >= (1LL << 31)) return fail(CA_EUNSUPPORTED, "cagpu_ga3c_grad: 2^31 rows or more in one call%s");
+  if (q->work_bytes < cagpu_ga3c_grad_work_bytes(q->rows))
+    return fail(CA_EINVAL, "cagpu_ga3c_grad: work_bytes is below cagpu_ga3c_grad_work_bytes(rows)%s");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (q->rows == 0) {
+    if (!q->accumulate && hipMemsetAsync(q->grad, 0, gg::G_TOTAL * sizeof(float), st) != hipSuccess)
+      return fail(CA_ELAUNCH, "cagpu_ga3c_grad: hipMemsetAsync failed%s");
+    return CA_OK;
+  }
+  gg::Args k;
+  std::memset(&k, 0, sizeof(k));
+  k.x = q->x; k.rows = static_cast<long>(q->rows); k.width = q->width; k.live = q->live;
+  k.dlogits = q->dlogits; k.dvalue = q->dvalue;
+  k.net = *net;
+  k.value_kernel = q->value_kernel;
+  k.work = static_cast<float*>(q->work);
+  k.l = gg::layout_of(k.rows);
+  const gg::Layout& l = k.l;
+  if (const int rc = launch(gg::prep_kernel, dim3(static_cast<unsigned>((gg::WT_TOTAL + 255) / 256)), dim3(256), 0, st, k.net,
+                            k.value_kernel, k.work))
+    return rc;
+  const unsigned grid = static_cast<unsigned>((k.rows + gg::T - 1) / gg::T);
+  std::snprintf(g_last_kernel, sizeof(g_last_kernel), "ga3c_grad_kernel grid=%u lds=%zu rows=%ld width=%d slices=%d%s%s%s%s", grid,
+                gg::LDS_BYTES, k.rows, k.width, l.slices, k.dlogits ? " logits" : "", k.dvalue ? " value" : "",
+                k.live ? " live" : "", q->accumulate ? " accumulate" : "");
+  if (const int rc = launch_lds(kernel_of<&gg::ga3c_grad_kernel>(), dim3(grid), dim3(gg::NT), gg::LDS_BYTES, st, k)) return rc;
+  gg::WArgs wa;
+  std::memset(&wa, 0, sizeof(wa));
+  const long R = k.rows;
+  //                   A      dZ     M        lda  K   ldz  N    out           ldo  bias
+  wa.job[0] = gg::WJob{l.xo,  l.dzl, R * 19,  7,   7,  256, 256, gg::G_LSTM_K, 256, gg::G_LSTM_B};
+  wa.job[1] = gg::WJob{l.hp,  l.dzl, R * 19,  64,  64, 256, 256, gg::G_LSTM_K + 7 * 256, 256, -1};
+  wa.job[2] = gg::WJob{l.a0,  l.dz1, R,       68,  68, 256, 256, gg::G_L1_K,   256, gg::G_L1_B};
+  wa.job[3] = gg::WJob{l.a1,  l.dz2, R,       256, 256, 256, 256, gg::G_L2_K,  256, gg::G_L2_B};
+  wa.job[4] = gg::WJob{l.a2,  l.dz3, R,       256, 256, 256, 256, gg::G_FC_K,  256, gg::G_FC_B};
+  wa.job[5] = gg::WJob{l.a3,  l.dzh, R,       256, 256, gg::NHEAD, 11, gg::G_P_K, 11, gg::G_P_B};
+  wa.job[6] = gg::WJob{l.a3,  l.dzh + 11, R,  256, 256, gg::NHEAD, 1, gg::G_V_K, 1, gg::G_V_B};
+  wa.work = k.work; wa.part = l.part; wa.slices = l.slices;
+  if (const int rc = launch(gg::wgrad_kernel, dim3(l.slices, 256 / gg::KB, gg::NJOBS), dim3(gg::NT), 0, st, wa)) return rc;
+  return launch(gg::reduce_kernel, dim3((gg::G_TOTAL + 255) / 256), dim3(256), 0, st,
+                static_cast<const float*>(k.work + l.part), l.slices, q->grad, q->accumulate ? 1 : 0);
+}
+
 // the generator's argument block from the entry points' arguments; `plain` / `ragged` name the caller in the messages
 static int gen_fail(const char* who, const char* text) {
   std::snprintf(g_err, sizeof(g_err), "%s: %s", who, text);

@@ -1174,6 +1174,48 @@ int cagpu_laserscan_slots(const CaParams *p, const CaPoseRing *ring, int32_t n_s
 int cagpu_laserscan_history(const CaParams *p, const CaScan *scan, const uint8_t *idx, const int32_t *step_num, int32_t n_steps,
                             int32_t first, int32_t count, uint8_t *hist_out, float *out, void *stream);
 
+/* ================================ GRADIENTS OF THE GA3C-CADRL NETWORK ================================
+ * The reference ships no training code for this network; the rule is this project's, and its judge is a float64 autograd
+ * evaluation of the graph tests/ga3c_f64_ref.py states (tests/ga3c_grad_ref.py is the backward pass written out).
+ *
+ * cagpu_ga3c_grad gives dL/d(weights) of the graph cagpu_ga3c_query evaluates, for upstream gradients on its two outputs:
+ * float32 normalisation of x, sequence length int(x[:,0]) clamped to 0..19, an LSTM-64 with gate order i, j, f, o and the
+ * forget gate's + 1 whose h and c are frozen behind a row's length, three ReLU layers (a ReLU passes gradient where its
+ * pre-activation is > 0), logits_p and logits_v.  Slots at and behind a row's length enter nothing: they are never read.
+ *
+ * grad: float32 [cagpu_ga3c_grad_floats() = 170 764], the concatenation in the checkpoint's key order and [in, out]
+ * row-major layout of lstm_kernel [71,256], lstm_bias [256], layer1_kernel [68,256], layer1_bias [256], layer2_kernel
+ * [256,256], layer2_bias [256], fc1_kernel [256,256], fc1_bias [256], logits_p_kernel [256,11], logits_p_bias [11],
+ * logits_v_kernel [256,1], logits_v_bias [1] (the last two are written as zeros when dvalue == NULL).  input_mean,
+ * input_std and x get no gradient.  The gradient is the plain SUM over the live rows of the row's vector-Jacobian product:
+ * a mean or a weighting is the caller's, through dlogits / dvalue.  accumulate == 0: grad is overwritten; accumulate == 1:
+ * the call's sum is added to what grad holds (a long batch in chunks under a workspace budget).
+ *
+ * Arithmetic: float32, every product an exact fused multiply-add on the vector ALU (no reduced-precision operand planes);
+ * the backward pass recomputes the activations it needs, the forward kernel is not involved.  DETERMINISTIC: the same inputs
+ * give the same bytes of grad whatever `work` held -- no atomics, the rows are summed in S = min(32, ceil(rows / 64))
+ * contiguous slices, each in row order, and the slices in slice order.  work: device memory, 4-byte aligned, of at least
+ * cagpu_ga3c_grad_work_bytes(rows) bytes (DESIGN.md says what it holds: about 36 KB per row + 0.7 MB per slice); it needs
+ * NO initialisation.  Non-finite inputs in live rows: unspecified.
+ *
+ * rows == 0: CA_OK, nothing launched, grad zeroed unless accumulate; x and work are not looked at (they may be NULL:
+ * cagpu_ga3c_grad_work_bytes(0) is 0), every other argument is checked as usual.  rows >= 2^31: CA_EUNSUPPORTED.  CA_EINVAL,
+ * grad untouched: NULL net / g / x / grad / work or weight pointer, rows < 0, width < 1, work_bytes too small, dlogits and
+ * dvalue both NULL, dvalue without value_kernel / value_bias.  net->packed, rows_scratch and agent_net are not used.
+ * cagpu_last_kernel() names the launch "ga3c_grad_kernel ...". */
+typedef struct CaNetGrad {
+  const float *x; int64_t rows; int32_t width, accumulate;   /* x, rows, width exactly as CaNetQuery (crop_x rule) */
+  const uint8_t *live;        /* [rows] or NULL: rows with live == 0 are NEVER READ (NaN there changes nothing) */
+  const float *dlogits;       /* [rows, 11] dL/d(logits_p/BiasAdd), or NULL (= 0) */
+  const float *dvalue;        /* [rows]     dL/d(Squeeze:0), or NULL (= 0); needs value_kernel / value_bias */
+  const float *value_kernel, *value_bias;
+  float *grad;                /* [cagpu_ga3c_grad_floats()] float32, see above */
+  void *work; uint64_t work_bytes;   /* >= cagpu_ga3c_grad_work_bytes(rows); needs NO initialisation */
+} CaNetGrad;                  /* 88 bytes */
+uint64_t cagpu_ga3c_grad_floats(void);                 /* host-only */
+uint64_t cagpu_ga3c_grad_work_bytes(int64_t rows);     /* host-only; 0 for bad arguments (and for rows == 0) */
+int cagpu_ga3c_grad(const CaNet *net, const CaNetGrad *g, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
